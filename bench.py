@@ -13,7 +13,13 @@ nic_nes_master.py:92-118), so rank r evaluates members [r P/N, (r+1) P/N) of the
 configs4 ('bu' features, pop=512; 64 per GPU on 8). --pop-per-gpu M is weak scaling (P = M N).
 
     python bench.py [--gpus N --steps K --warmup W] [--preset metric|configs1|configs2|configs3|configs4]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print the line.
+--full adds what takes work of its own: the cpu_baseline leg (the restated reference worker on the host
+cores) and the lookup of the committed PMC profile behind roofline.traffic / mfma_busy (it disassembles the
+library). --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 
 --gpus N without a launcher (no WORLD_SIZE in the environment) starts N rank processes itself, before
 anything touches the GPU, with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set
@@ -216,6 +222,18 @@ def cpu_baseline(args, B, P):
                                     'rate (linear, an upper bound for the reference)'}
 
 
+def dump_outputs(path, runner, eng, ratio):
+    """What a caller of the timed path holds after its last step, as <path>/<name>.npy: the whole population's
+    fitness [P, 2] (f+, f-; fp64), the weighted noise sum the update formed [D] (fp32, after its all-reduce), the
+    theta Adam left [D] (fp64) and the update ratio [1] (fp64). About 34 MB at the default model size. The
+    workload is seeded, so two builds run with the same arguments can be compared array for array."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {'fitness': runner.fit_all, 'noise_sum': runner.gsum, 'theta': eng.theta()[0]}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy())
+    np.save(os.path.join(path, 'update_ratio.npy'), np.array([ratio], np.float64))
+
+
 def resolve_world(gpus, env):
     """(world, launched_here): the rank count this run uses. `gpus` is --gpus (None: not given).
     Under a launcher (WORLD_SIZE set) --gpus must name the same count; without one, --gpus N > 1 means
@@ -375,7 +393,11 @@ def main():
                     help="model_options.safe_mutations (mscoco_nes.json: '', underflow 0.1): the per-task mutation "
                     "vector is recomputed from each iteration's theta on the host (nicnes.mutations) inside the "
                     "timed step, as reference workers do per task")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also what the headline figure does not need: the '
+                    'cpu_baseline leg and the committed PMC profile behind roofline.traffic (default: off)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the cpu_baseline leg')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the arrays the last timed step '
+                    'computed (fitness, noise sum, theta, update ratio) as DIR/<name>.npy')
     ap.add_argument('--decode-split', type=int, default=0, help='force S logit workgroups per member (0 = auto)')
     ap.add_argument('--decode-rows', type=int, default=0, help='force 4 (128-row) or 2 (64-row) slabs (0 = auto)')
     ap.add_argument('--cpu-cores', type=int, default=0, help='worker processes (0: cpu_count()-2 capped by the usable CPUs)')
@@ -410,9 +432,9 @@ def main():
             raise SystemExit(3)
         return
 
-    # CPU leg first, before this process touches the GPU (its pool forks)
+    # CPU leg (--full) first, before this process touches the GPU (its pool forks)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, B, P)
 
     import torch
@@ -511,6 +533,8 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     ratio = eng.last_ratio()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runner, eng, ratio)
     # decode timing of the last timed step (HIP events recorded between its launches)
     dec_ms.append(eng.kernel_times()[0])
     phases.append(eng.decode_phase_times())
@@ -599,14 +623,14 @@ def main():
     # (the instantiation the last timed decode ran: the greedy-only bounded-lse one, or the exact one -- log-probs
     # written, NICNES_BOUNDED_LSE=0, or the engine's adaptive policy on a peaked theta)
     pairs_run = args.fitness == 'greedy' and eng.last_decode_bounded()
-    pmc, pmc_stale = load_pmc(kname, P_local, B, pairs_run)
+    pmc, pmc_stale = load_pmc(kname, P_local, B, pairs_run) if args.full else (None, None)
     traffic = pmc['derived'].get('hbm_bytes_per_launch') if pmc else None
     hbm_peak_bytes = HBM_PEAK_GBS * 1e9 * step_ms / 1e3
     iter_bytes = iteration_algorithmic_bytes(B, P_local)
     out = {
         'metric': METRIC, 'value': round(value, 3), 'unit': 'members/s', 'n_gpus': world, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True,
-        'scaling': scaling, 'vs_baseline': None, 'dtype': 'fp32',
+        'full': bool(args.full), 'scaling': scaling, 'vs_baseline': None, 'dtype': 'fp32',
         'data': 'synthetic (seeded fc features, xavier-init fc_caption theta, substituted refs, 2^27 noise table)',
         'config': {'baseline_config': args.preset if not (args.population or args.pop_per_gpu or args.batch)
                    else 'custom (%s preset overridden)' % args.preset,
@@ -642,6 +666,7 @@ def main():
                      'traffic_source': pmc['file'] if pmc else None,
                      'traffic_kernel_symbol': pmc.get('kernel_symbol') if pmc else None,
                      'traffic_stale': pmc_stale,
+                     'traffic_looked_up': bool(args.full),
                      'hbm_frac': round(alg_bytes / hbm_peak_bytes, 4),
                      'hbm_frac_counters': round(traffic / hbm_peak_bytes, 4) if traffic else None,
                      'mfma_busy': round(pmc['derived']['mfma_busy'], 4) if pmc and 'mfma_busy' in pmc['derived'] else None,

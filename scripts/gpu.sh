@@ -21,7 +21,7 @@ ACT=${2:?ACTION}
 shift 2
 O=gpurun_out/$TAG
 mkdir -p $O
-B="python3 -u bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+B="python3 -u bench.py --steps 10 --warmup 2 --full --no-cpu-baseline"
 case $ACT in
   tests)
     T=${1:-all}
@@ -33,7 +33,7 @@ case $ACT in
     NICNES_BENCH_SHARE_GPU=1 NICNES_BENCH_BACKEND=gloo timeout -k 10 300 python -u bench.py --gpus 2 --steps 10 \
       --warmup 2 > $O/bench_2rank_shared.json 2> $O/bench_2rank_shared.err ;;
   benchset)
-    timeout -k 10 400 python3 -u bench.py > $O/bench_default.json 2> $O/bench_default.err
+    timeout -k 10 400 python3 -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err
     for P in 256 128 64; do
       timeout -k 10 200 $B --population $P > $O/bench_pop$P.json 2> $O/bench_pop$P.err
     done
@@ -45,12 +45,12 @@ case $ACT in
     timeout -k 10 200 $B --fitness greedy_linprob > $O/bench_linprob.json 2> $O/bench_linprob.err
     timeout -k 10 200 $B --theta-gain 4 --bias-std 0.1 > $O/bench_trained_like_theta.json 2> $O/bench_trained_like_theta.err
     timeout -k 10 300 $B --batches 64 > $O/bench_batches64.json 2> $O/bench_batches64.err
-    timeout -k 10 300 python3 -u bench.py --steps 5 --warmup 1 --no-cpu-baseline --mutation SM-G-SUM > $O/bench_smgsum.json 2> $O/bench_smgsum.err
-    timeout -k 10 300 python3 -u bench.py --steps 5 --warmup 1 --no-cpu-baseline --mutation SM-PROPORTIONAL > $O/bench_smprop.json 2> $O/bench_smprop.err
+    timeout -k 10 300 python3 -u bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --mutation SM-G-SUM > $O/bench_smgsum.json 2> $O/bench_smgsum.err
+    timeout -k 10 300 python3 -u bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --mutation SM-PROPORTIONAL > $O/bench_smprop.json 2> $O/bench_smprop.err
     for F in sample self_critical sc_loss; do
-      timeout -k 10 300 python3 -u bench.py --steps 5 --warmup 1 --no-cpu-baseline --fitness $F > $O/bench_fitness_$F.json 2> $O/bench_fitness_$F.err
+      timeout -k 10 300 python3 -u bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --fitness $F > $O/bench_fitness_$F.json 2> $O/bench_fitness_$F.err
     done
-    timeout -k 10 300 python3 -u bench.py --steps 5 --warmup 1 --no-cpu-baseline --fitness sample --theta-gain 4 \
+    timeout -k 10 300 python3 -u bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --fitness sample --theta-gain 4 \
       --bias-std 0.1 > $O/bench_sample_trained_like.json 2> $O/bench_sample_trained_like.err ;;
   ab)
     export ABLATE_DIR=ablate_libs EXACT=${2:-}

@@ -68,6 +68,17 @@ def test_launcher_starts_n_ranks():
     assert len({d['MASTER_PORT'] for d in seen}) == 1 and {d['MASTER_ADDR'] for d in seen} == {'127.0.0.1'}
 
 
+def test_full_and_dump_outputs_reach_every_rank(tmp_path):
+    """--full and --dump-outputs DIR are options of the rank processes too (the launcher forwards its arguments);
+    a dry run writes nothing."""
+    p = _run(['--gpus', '2', '--population', '64', '--full', '--dump-outputs', str(tmp_path / 'dump')],
+             {'NICNES_BENCH_DRY_RANKS': '1', 'NICNES_BENCH_SHARE_GPU': '1'})
+    assert p.returncode == 0, p.stderr
+    seen = [json.loads(l) for l in (p.stdout + p.stderr).splitlines() if l.startswith('{')]
+    assert sorted(d['members'] for d in seen) == [[0, 32], [32, 64]]
+    assert not (tmp_path / 'dump').exists()
+
+
 def test_launcher_returns_a_failing_ranks_status():
     p = _run(['--gpus', '2'], {'NICNES_BENCH_DRY_RANKS': '1', 'NICNES_BENCH_SHARE_GPU': '1',
                                'NICNES_BENCH_DRY_FAIL_RANK': '1'})
