@@ -329,6 +329,24 @@ int nicnes_decode_path(nicnes_handle* h, int32_t B, int32_t count, int32_t* out_
  * exact stretch after a bounded decode needed exact passes). Measurement bookkeeping for bench.py (which kernel
  * instantiation a line's PMC counters belong to); no reference counterpart. */
 int nicnes_last_decode_lse(nicnes_handle* h, int32_t* bounded_host);
+/* Screened decode (not a reference interface): mode 1 runs the logit loop of the fused greedy-only decode
+ * (128-row slabs, one workgroup per member slab, pair-bounded lse, no log-probs, plain mutations) in bf16 and certifies
+ * the candidate tokens it leaves with exact fp32 chains; mode 0 the fp32 loop; mode 2 (the default) screens when the
+ * decode has more workgroups (members x slabs) than the GPU has CUs, where it is faster. Tokens do not depend on it.
+ * env NICNES_SCREEN=0/1/2 sets the initial value; test hook NICNES_SCREEN_EPS_SCALE (>= 1) widens the screening bound. */
+int nicnes_set_decode_screen(nicnes_handle* h, int32_t mode);
+/* the screened decodes' counters since create: [0] candidate ids captured, [1] rows that sent their
+ * workgroup's step to the fp32 loop */
+int nicnes_screen_stats(nicnes_handle* h, int64_t* out2_host);
+/* Test entry (no reference counterpart): every vocabulary logit of member `member` of `iteration` at sigma, sign
+ * (0: +, 1: -), over 32 given rows of h (h_rows_dev [32, 128] fp32, unit order), computed twice: out_mfma_dev by the
+ * 32-row fp32 MFMA tile path of the exact pass, out_chain_dev by the function the screened decode certifies with (one
+ * lane's fmaf chain in the MFMA's k order, nicnes_math.h nn_kperm), both reading h from the engine's lane scratch in
+ * the decode's layout (so no decode may run beside it), both [32, vocab_size + 1] fp32 on the device. The two are equal bit for bit: that is what
+ * lets a screened decode certify a candidate's exact logit without staging a tile. Plain mutations
+ * only. Asynchronous on stream. */
+int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
+                            const float* h_rows_dev, float* out_mfma_dev, float* out_chain_dev, void* stream);
 
 #ifdef __cplusplus
 }

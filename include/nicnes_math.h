@@ -169,4 +169,32 @@ NN_FN int nn_kperm(int pos) {
     return (chunk << 5) + (j & 3) + 8 * (j >> 2) + 4 * half;
 }
 
+/*
+ * Screening bound ("bf16 screening"). A logit L is the fp32 chain above over w = fp32(W0 +/- delta),
+ * h and the bias b. A screened logit l~ is the same sum taken by a bf16 MFMA: both operands rounded to bf16 (RNE,
+ * unit roundoff 2^-8), products accumulated in fp32 from b in an order the hardware does not document.
+ * nn_screen_eps bounds |l~ - L| for every row of a (member, sign) from three numbers: hnorm >= ||h||_2,
+ * wnorm >= max_v ||w_v||_2, babs >= max_v |b_v|. With P = hnorm * wnorm >= sum_k |w_k h_k| (Cauchy-Schwarz):
+ *   operand roundings   ((1 + 2^-8)^2 - 1) P = (2^-7 + 2^-16) P, taken as (2^-7 + 2^-15) P;
+ *   accumulations       the MFMA's 128 products + bias, each add truncated (2^-23 of the partial sum, partial
+ *                       sums <= |b| + (1 + 2^-7 + 2^-16) P): < 2^-15.9 (babs + P); the fp32 chain's 128 roundings
+ *                       against the real sum: 2^-17 (babs + P); together < 2^-15.5 (babs + P), taken as 2^-13;
+ *   subnormals          bf16 rounds a subnormal absolutely (2^-134), products and flushed operands lose at most
+ *                       2^-126 each: < 2^-119 (1 + hnorm + wnorm), taken as 2^-116.
+ * scale >= 1 widens the two relative terms (a test hook). A non-finite result sends the row to the exact pass.
+ */
+NN_FN float nn_screen_eps(float hnorm, float wnorm, float babs, float scale) {
+    const float P = hnorm * wnorm;
+    const float rel = 0.0078430175781250f * P + 0.0001220703125f * (babs + P);   /* 2^-7 + 2^-15, 2^-13 */
+    return scale * rel + nn_pow2i(-116) * (1.0f + hnorm + wnorm);
+}
+
+/*
+ * nn_screen_norm: an upper bound of ||x||_2 from the fp32 sum of squares ss (any summation order: n - 1 roundings
+ * of non-negative terms, n <= 128, halve under the root; 2^-16 covers them, the root's and the roundings inside
+ * nn_screen_eps) plus 2^-58 for squares that underflowed (below 2^-126 they may be flushed: 128 of them are less
+ * than 2^-119 of ss, 2^-59.5 of the root).
+ */
+NN_FN float nn_screen_norm(float ss) { return sqrtf(ss) * 1.0000152587890625f + nn_pow2i(-58); }
+
 #endif /* NICNES_MATH_H */

@@ -3,6 +3,7 @@
 #define SCR_SLOTS (64 + 64 + 64 + 1 + 64)   // per lane: c | h' | x of t = 0 | unfinished | h' (odd parity, split path)
 #define PART_FLOATS (8 * 7 * 64)             // split path: partial greedy state of one logit workgroup (8 waves x 7 x 64 lanes)
 #define COOP_CTR_STRIDE 32                   // coop path: uint32 per member-slab hand-off counter (its own 128-byte line)
+#define SCREEN_CAP_WORDS(V1) ((size_t)(((V1) + 63) / 64) * 512)   // screened decode: one word per 64-row stage and thread
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,6 +52,16 @@ struct DecodeParams {
     int64_t off_img_w, off_img_b, off_emb_w, off_log_w, off_log_b, off_i2h_w, off_i2h_b, off_h2h_w, off_h2h_b;
 };
 
+// The screened decode's own arguments (the screened kernels' second argument: DecodeParams, and with it every other
+// kernel's argument layout and machine code, stays as it is). cap == NULL: no screening.
+struct ScreenArgs {
+    uint32_t* cap;               // [members * slabs] capture slots of SCREEN_CAP_WORDS(V1) words: [stage][thread]
+    float* norm;                 // [members][4]: max_v |w+_v|^2, max_v |w-_v|^2, max_v |b+_v|, max_v |b-_v| of the
+                                 // member's logit rows (nicnes_screen_norm_kernel, before the decode)
+    float scale;                 // >= 1, multiplies eps (test hook NICNES_SCREEN_EPS_SCALE)
+    unsigned long long* ctr;     // [0] candidate ids captured, [1] rows that sent their step to the fp32 loop (atomic)
+};
+
 // A mutated decode on the fused greedy path (mode != 0; the kernels' second argument, so the other kernels' argument
 // layout is untouched): the delta' rows in DecodeParams::noise hold only the parameters from off_log_w on (logit, i2h,
 // h2h: re-read at every step); the image projection and the embedding rows (read once, and only for the tokens taken)
@@ -83,13 +94,18 @@ extern "C" hipError_t nicnes_decode_init();
 extern "C" hipError_t nicnes_decode_occupancy(int* coop_per_cu, int* sample_per_cu);
 // shifts the per-member and per-workgroup pointers of *p to member m0 (a decode of members m0.. on
 // its own stream; nslabs = the launch's row slabs)
-extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead* mh);
+extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead* mh, ScreenArgs* sa = nullptr);
 // mh: nullable (or mode 0): no decode-formed delta'
 extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead* mh, int member_count, int nslabs,
-                                           hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch);
+                                           hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch,
+                                           const ScreenArgs* sa = nullptr);   // sa: nullable (or cap NULL): the fp32 loop
 // zero seq_logprobs past the batch's last finishing step (rollouts = members x 2 of B rows; after a
 // no_exit decode of a batch spanning several slabs)
 extern "C" hipError_t nicnes_launch_lp_batch_exit(const int32_t* seq, float* lp, int rollouts, int B, int T,
                                                   hipStream_t stream);
+// test entry (nicnes_test_logit_chain): the logits of the member slice at nidx, sign sgn, over hin [32, 128], by the
+// 32-row MFMA tile path and by the fmaf chain; reads theta, noise, scratch (one wave's lane scratch), V1, D, off_log_w, off_log_b of *p
+extern "C" hipError_t nicnes_launch_test_logit_chain(const DecodeParams* p, uint64_t nidx, int sgn, const float* hin,
+                                                     float* out_mfma, float* out_chain, hipStream_t stream);
 // lane scratch for up to member_count members x row_waves 32-row waves of one sign
 extern "C" size_t nicnes_decode_scratch_floats(int member_count, int row_waves_per_member);

@@ -35,6 +35,8 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 #define NTHREADS 512
@@ -42,7 +44,10 @@ typedef __amdgpu_buffer_rsrc_t rsrc_t;
 #define SIGN_FLOATS (32 * LDS_ROW)
 #define STAGE_FLOATS (2 * SIGN_FLOATS + 64)           // 32-row stage: W+ | W- | bias+ (32) | bias- (32)
 #define STAGE64_FLOATS (2 * 64 * LDS_ROW + 128)       // 64-row stage: W+ | W- | bias+ (64) | bias- (64)
+#define BF_ROW 68                                     // screened stage: dwords per bf16 row (128 k + 8 pad: as LDS_ROW, 4 mod 32)
+#define BF_SIGN (64 * BF_ROW)                         // screened 64-row stage: W+ | W- (bf16) | bias+ (64) | bias- (64) (fp32)
 #define LOG2E 1.44269504088896340736f
+#define H_SLOT_BYTES (4u * 64u * 64u)                 // byte offset of H_SLOT(0) in a wave's lane scratch (below)
 #define NEG_INF (-__builtin_inff())
 
 #ifndef DECODE_ABLATE
@@ -430,6 +435,64 @@ __device__ __forceinline__ void mfma_stage64_o(const float* w, const float* bias
     at(8);
 }
 
+// ---- screened (bf16) 64-row stages ---------------------------------------------------------------------------
+// The tile is formed as fp32(W0 +/- delta), as stage64_store_o forms it, then rounded to bf16 (v_cvt_pk_bf16_f32, RNE)
+// into the same column order at half the width; the bias stays fp32 (the accumulator's start). Padded rows get a
+// large finite bias in place of -inf: screened logits are only compared and summed, and stay finite.
+#define SCREEN_PAD (-1.0e30f)
+// LaneOffs::so and ::arow of a screened stage (BF_ROW dwords per row)
+struct LaneOffsBf {
+    int sob, arowb;
+};
+__device__ __forceinline__ LaneOffsBf lane_offs_bf(int wave) {
+    LaneOffsBf o;
+    const int lane = lane_fresh(), tid = wave * 64 + lane, q = tid & 31;
+    o.sob = (tid >> 5) * BF_ROW + (q >> 3) * 16 + (q & 1) * 8 + 2 * ((q & 7) >> 1);
+    o.arowb = (lane & 31) * BF_ROW + 8 * (lane >> 5);
+    return o;
+}
+
+__device__ __forceinline__ void stage64_store_bf(float* buf, int valid, const LaneOffs& o, int sob, bool bias,
+                                                 const Stage64Regs& r) {
+    float* b = buf + sob;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const f32x4 delta = r.z[u];
+        *reinterpret_cast<bf16x4*>(b + 16 * u * BF_ROW) = __builtin_convertvector(r.w[u] + delta, bf16x4);
+        *reinterpret_cast<bf16x4*>(b + (64 + 16 * u) * BF_ROW) = __builtin_convertvector(r.w[u] - delta, bf16x4);
+    }
+    if (bias) {
+        const float delta = r.bz;
+        const float v = o.bslot >= 64 ? r.bw - delta : r.bw + delta;
+        buf[2 * BF_SIGN + o.bslot] = (o.bslot & 63) < valid ? v : SCREEN_PAD;
+    }
+}
+
+// two chains of 8 v_mfma_f32_32x32x16_bf16 over Bb = h in bf16: MFMA n takes from lane half hh the 8 k that the fp32
+// chains' MFMAs 8n .. 8n + 7 take from it (A and B agree on that set; the order inside a product sum is the
+// hardware's). mid() runs before MFMA pair MID of 8.
+template <int MID = 8, class Mid = NoMid>
+__device__ __forceinline__ void mfma_stage64_bf(const float* w, const float* bias, const bf16x8 (&Bb)[8], int arowb,
+                                                int hh, f32x16& acc0, f32x16& acc1, Mid&& mid = Mid()) {
+    const float* row0 = w + arowb;
+    const float* row1 = row0 + 32 * BF_ROW;
+    acc0 = bias_init(bias, hh);
+    acc1 = bias_init(bias + 32, hh);
+#pragma unroll
+    for (int n = 0; n < 8; ++n) {
+        if (n == MID) {
+            __builtin_amdgcn_sched_barrier(0);
+            mid();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(row0 + 16 * (n >> 1) + 4 * (n & 1));
+        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(row1 + 16 * (n >> 1) + 4 * (n & 1));
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, Bb[n], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, Bb[n], acc1, 0, 0, 0);
+    }
+    if (MID == 8) mid();
+}
+
 template <int MID = 8, class Mid = NoMid>
 __device__ __forceinline__ f32x16 mfma_tile_o(f32x16 acc, const float* w, const float (&Bop)[64], int arow,
                                               Mid&& mid = Mid()) {
@@ -796,6 +859,7 @@ __device__ __forceinline__ double samp_scale(double x, float e) {
 // place of the greedy epilogue
 struct NoHook {
     static constexpr bool replaces = false;
+    static constexpr bool bf = false;                 // bf: the stages are staged and multiplied in bf16 (ScreenStage)
     __device__ __forceinline__ void operator()(const f32x16&, const f32x16&, int) const {}
 };
 
@@ -805,6 +869,7 @@ struct NoHook {
 // (+2.5 %), the early sign's logit stores before them (+0.7 %), sc1 / sc0 sc1 / sc1 nt logit stores (+1-2 %).
 struct SampleStage {
     static constexpr bool replaces = true;
+    static constexpr bool bf = false;
     rsrc_t slot;
     uint32_t vo;      // 16 * lane + SLOG_WAVE_BYTES * wave
     uint32_t vb;      // 16 * lane + 1024 * wave (block records)
@@ -1046,6 +1111,203 @@ __device__ __forceinline__ void sample_pick(const DecodeParams& p, rsrc_t lr, ui
     else { tok = other; lpv = olp; }
 }
 
+// ---- screened greedy decode ("bf16 screening") ---------------------------------------------------
+// The logit loop runs in bf16 (16x the fp32 MFMA rate): its logits l~ lie within eps (nn_screen_eps) of the exact
+// ones, so every id that can be the greedy token has l~ >= m~ - 2 eps - hu_out (m~ the screened row maximum, hu_out
+// tie_window's outer half-ulp). ScreenStage keeps the screened max and pair-bounded exp-sum as epilogue64<PAIRS> does
+// and leaves one word per lane and stage in the workgroup's capture slot: the largest of the lane's 16 pair maxima
+// with its low five mantissa bits replaced by the pair's index (bits 0-3) and a crowded flag (bit 4: a second pair
+// maximum within `delta` of it, delta >= 2 eps + hu_out). After the loop screen_certify scans the lane's words against
+// the final threshold and computes the exact logits of the ids behind each hit (the pair, or all 32 of a crowded
+// lane-stage) with logit_chain, in id order, into the same records the fp32 loop keeps. A step the records cannot
+// decide is run again by the fp32 loop itself (step_body).
+#define SCREEN_PACK_REL 1.52587890625e-05f   // 2^-16: the word is within 2^-18 |q| of the pair maximum it encodes
+#define SCREEN_HU_MAX 1.9073486328125e-06f   // 2^-19: tie_window's hu_out while lse < 64
+#define SCREEN_HIT_CAP 8                     // hit lane-stages one lane certifies (a crowded one counts 4); more: the fp32 loop
+struct ScreenStage {
+    static constexpr bool replaces = true;
+    static constexpr bool bf = true;
+    rsrc_t cap;                  // the workgroup's capture slot
+    uint32_t vo;                 // 4 * thread
+    float delta;                 // 2 eps + SCREEN_HU_MAX
+    const bf16x8 (&Bb)[8];
+    RowState& st;
+    __device__ __forceinline__ void operator()(const f32x16& P0, const f32x16& P1, int s) const {
+        if (s < 0) return;                               // the pipeline's first epilogue: no stage yet
+        float q[16];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            q[r] = vmax2(P0[2 * r], P0[2 * r + 1]);
+            q[8 + r] = vmax2(P1[2 * r], P1[2 * r + 1]);
+        }
+        const float a0 = vmax3(q[0], q[1], q[2]), a1 = vmax3(q[3], q[4], q[5]), a2 = vmax3(q[6], q[7], q[8]);
+        const float a3 = vmax3(q[9], q[10], q[11]), a4 = vmax3(q[12], q[13], q[14]);
+        const float tmax = vmax3(vmax3(a0, a1, a2), a3, vmax2(a4, q[15]));
+        // the same maximum over the pair maxima made finite (NaN and -inf -> -3e38) with the index in the low bits
+        float k[16];
+        const float lim = tmax - delta;
+        int cnt = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float f = __builtin_amdgcn_fmed3f(q[r], -3.0e38f, 3.0e38f);
+            k[r] = __builtin_bit_cast(float, (__builtin_bit_cast(uint32_t, f) & ~31u) | (uint32_t)r);
+            cnt += q[r] >= lim ? 1 : 0;
+        }
+        const float b0 = vmax3(k[0], k[1], k[2]), b1 = vmax3(k[3], k[4], k[5]), b2 = vmax3(k[6], k[7], k[8]);
+        const float b3 = vmax3(k[9], k[10], k[11]), b4 = vmax3(k[12], k[13], k[14]);
+        const float kmax = vmax3(vmax3(b0, b1, b2), b3, vmax2(b4, k[15]));
+        const uint32_t word = __builtin_bit_cast(uint32_t, kmax) | (cnt >= 2 ? 16u : 0u);
+        __builtin_amdgcn_raw_buffer_store_b32(word, cap, (int)vo, (int)(2048u * (uint32_t)s), 0);
+        const float mnew = vmax2(st.m, tmax);
+        const float ml = mnew * LOG2E;
+        float sum = st.s * __builtin_amdgcn_exp2f((st.m - mnew) * LOG2E);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sum += __builtin_amdgcn_exp2f(__builtin_fmaf(q[r], LOG2E, -ml));
+        st.s = sum;
+        st.m = mnew;
+    }
+};
+
+// one candidate into the lane's records (records4's update for one id; ids arrive in increasing order)
+__device__ __forceinline__ void record1(RowState& st, float L, int v) {
+    const bool c = L > st.r1v;
+    st.ev = c ? st.r0v : st.ev;
+    st.r0v = c ? st.r1v : st.r0v;
+    st.r0i = c ? st.r1i : st.r0i;
+    st.r1v = c ? L : st.r1v;
+    st.r1i = c ? v : st.r1i;
+}
+
+// One lane's exact logit of vocabulary id v for the row at row_lo = 4 * (lane & 31) of the wave's lane scratch: the
+// fp32 chain acc = fmaf(w_k, h_k, acc) from the bias, with w = fp32(W0 +/- delta) formed as the staging forms it and k
+// in the order the MFMA chains consume it (nn_kperm: MFMA 16T + jj takes k = 32T + 8(jj / 4) + jj % 4 from lane half 0,
+// then that + 4 from half 1). h comes from the scratch as the cell left it: H_SLOT(i) of lane half hh holds unit
+// nn_kperm(2 i + hh) of the row, the partner half 128 bytes on. The fp32 MFMA is that fmaf chain bit for bit, so this
+// equals mfma_tile's and mfma_stage64_o's accumulator for (v, row) without staging a tile; the test entry below runs
+// this function against mfma_tile over the whole vocabulary (tests/test_gpu_screen.py).
+__device__ __forceinline__ float logit_chain(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, int v, int sgn,
+                                                 rsrc_t scr_r, uint32_t row_lo) {
+    const uint32_t wo = 4u * ((uint32_t)p.off_log_w + 128u * (uint32_t)v), bo = 4u * ((uint32_t)p.off_log_b + (uint32_t)v);
+    const float bw = ld1(theta_r, bo), bz = ld1(noise_r, bo);
+    float acc = sgn ? bw - bz : bw + bz;
+#pragma unroll
+    for (int T = 0; T < 4; ++T) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint32_t ko = 4u * (uint32_t)(32 * T + 8 * c);
+            const f32x4 w0 = ld4(theta_r, wo + ko), z0 = ld4(noise_r, wo + ko);
+            const f32x4 w1 = ld4(theta_r, wo + ko + 16u), z1 = ld4(noise_r, wo + ko + 16u);
+            const f32x4 a0 = sgn ? w0 - z0 : w0 + z0, a1 = sgn ? w1 - z1 : w1 + z1;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                // slot 16T + 4c + e: unit 32T + 8c + e in lane half 0, that + 4 in half 1
+                const uint32_t so = H_SLOT_BYTES + 256u * (uint32_t)(16 * T + 4 * c + e);
+                acc = __builtin_fmaf(a0[e], ld1(scr_r, row_lo, so), acc);
+                acc = __builtin_fmaf(a1[e], ld1(scr_r, row_lo + 128u, so), acc);
+            }
+        }
+    }
+    return acc;
+}
+
+// The lane's words against thr (already lowered by the packing error): exact logits of the ids behind every hit into
+// st's records. Returns false when the lane would certify more than SCREEN_HIT_CAP lane-stages (the step goes to the
+// fp32 loop). ncand counts the candidate ids captured.
+__device__ __forceinline__ bool screen_certify(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, rsrc_t scr_r,
+                                               rsrc_t cap, uint32_t vo, int nst, int sgn, int hh, uint32_t row_lo,
+                                               float thr, float* lds, int tid, RowState& st, int& ncand) {
+    // pass 1: the lane's hit lane-stages, in stage order, into its private list in LDS (free between the logit loop's
+    // last barrier and the token phase's): entry = stage << 8 | crowded << 4 | pair
+    uint32_t* list = reinterpret_cast<uint32_t*>(lds) + tid * SCREEN_HIT_CAP;
+    int cnt = 0, hits = 0;
+    for (int s0 = 0; s0 < nst; s0 += 16) {
+        uint32_t wd[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            wd[j] = __builtin_amdgcn_raw_buffer_load_b32(cap, (int)vo, (int)(2048u * (uint32_t)min(s0 + j, nst - 1)), 0);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const uint32_t word = wd[j];
+            if (s0 + j < nst && __builtin_bit_cast(float, word & ~31u) >= thr) {
+                hits += (word & 16u) ? 4 : 1;
+                ncand += (word & 16u) ? 32 : 2;           // candidate ids captured (certified below unless over the cap)
+                if (cnt < SCREEN_HIT_CAP) list[cnt] = ((uint32_t)(s0 + j) << 8) | (word & 31u);
+                ++cnt;
+            }
+        }
+    }
+    if (hits > SCREEN_HIT_CAP) return false;
+    // pass 2: hit k of every lane at once (the wave runs as many rounds as its busiest lane has hits)
+    for (int k = 0; k < SCREEN_HIT_CAP; ++k) {
+        if (!__any(k < cnt)) break;
+        if (k < cnt) {
+            const uint32_t e = list[k];
+            const int s = (int)(e >> 8), pr = (int)(e & 15u);
+            const bool crowded = (e & 16u) != 0;
+            // acc index a of chain c (P0 / P1): id 64 s + 32 c + 4 hh + (a & 3) + 8 (a >> 2), increasing in (c, a)
+            const int i0 = crowded ? 0 : 2 * pr, i1 = crowded ? 32 : 2 * pr + 2;
+            for (int i = i0; i < i1; ++i) {
+                const int a = i & 15;
+                const int v = 64 * s + 32 * (i >> 4) + 4 * hh + (a & 3) + 8 * (a >> 2);
+                if (v < p.V1) {
+                    record1(st, logit_chain(p, theta_r, noise_r, v, sgn, scr_r, row_lo), v);
+                }
+            }
+        }
+    }
+    return true;
+}
+
+// max_v |w_v|^2 and max_v |b_v| of a member's logit rows, both signs (ScreenArgs::norm): one workgroup per
+// member, 32 threads per row. An inf or NaN entry (or a sum of finite squares that overflows) makes the maximum inf or
+// NaN, which sticks: eps is then not finite and every step of the member runs the fp32 loop.
+__global__ __launch_bounds__(NTHREADS) void nicnes_screen_norm_kernel(DecodeParams p, ScreenArgs sa) {
+    __shared__ float red[4][8];
+    const int tid = threadIdx.x, q = tid & 31, member = blockIdx.x;
+    const uint64_t nidx = p.noise_idx[member];
+    const rsrc_t w_r = make_rsrc(p.theta + p.off_log_w, 4u * 128u * (uint32_t)p.V1);
+    const rsrc_t z_r = make_rsrc(p.noise + nidx + p.off_log_w, 4u * 128u * (uint32_t)p.V1);
+    const rsrc_t b_r = make_rsrc(p.theta + p.off_log_b, 4u * (uint32_t)p.V1);
+    const rsrc_t bz_r = make_rsrc(p.noise + nidx + p.off_log_b, 4u * (uint32_t)p.V1);
+    float m[4] = {0.f, 0.f, 0.f, 0.f};
+    auto upd = [](float& mx, float x) { mx = (x > mx || x != x) ? x : mx; };
+    for (int v = tid >> 5; v < p.V1; v += NTHREADS / 32) {
+        const uint32_t off = 4u * (uint32_t)(128 * v + 4 * q);
+        const f32x4 w = ld4(w_r, off), z = ld4(z_r, off);
+        const f32x4 a = w + z, b = w - z;
+        float ssp = 0.f, ssm = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            ssp += a[e] * a[e];
+            ssm += b[e] * b[e];
+        }
+#pragma unroll
+        for (int d = 16; d >= 1; d >>= 1) {
+            ssp += __shfl_xor(ssp, d);
+            ssm += __shfl_xor(ssm, d);
+        }
+        upd(m[0], ssp);
+        upd(m[1], ssm);
+    }
+    for (int v = tid; v < p.V1; v += NTHREADS) {
+        const float bw = ld1(b_r, 4u * (uint32_t)v), bz = ld1(bz_r, 4u * (uint32_t)v);
+        upd(m[2], fabsf(bw + bz));
+        upd(m[3], fabsf(bw - bz));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) upd(m[i], __shfl_xor(m[i], d));
+        if ((tid & 63) == 0) red[i][tid >> 6] = m[i];
+    }
+    __syncthreads();
+    if (tid < 4) {
+        float r = red[tid][0];
+        for (int w = 1; w < 8; ++w) upd(r, red[tid][w]);
+        sa.norm[4 * member + tid] = r;
+    }
+}
+
 // Measured and not kept (git history, r04): per-wave LDS progress words in place of the per-stage barrier (+0.4 %),
 // a chain-a-only last stage for the coop ranges (+1.3 % / +2.2 % at P = 64 / 128, or spills inside the loop).
 template <int G, bool PAIRS, bool PEEL = true, class Tail = NoTail, class Hook = NoHook>
@@ -1066,10 +1328,16 @@ __device__ __forceinline__ void logit_stages(float* lds, const DecodeParams& p, 
         return Sx;
     };
     const LaneOffs lo = lane_offs(wave, 128u);
+    LaneOffsBf lob{0, 0};
+    if constexpr (Hook::bf) lob = lane_offs_bf(wave);
     const int hh = lane_fresh() >> 5, vl = 4 * hh + (G == 4 ? 0 : 32 * hf);
     const bool bias = wave < 2;
     if (!preloaded) stage64_load_o(lsrc(s0), lo, bias, s64);
-    stage64_store_o(lds, lsrc(s0).valid, lo, bias, s64);
+    auto sstore = [&](float* buf, int valid) __attribute__((always_inline)) {
+        if constexpr (Hook::bf) stage64_store_bf(buf, valid, lo, lob.sob, bias, s64);
+        else stage64_store_o(buf, valid, lo, bias, s64);
+    };
+    sstore(lds, lsrc(s0).valid);
     // the registers carry stage s + 1 into stage s: its W+- tile is written before the last quarter of the
     // MFMAs of stage s (its buffer was last read in stage s - 1), then the loads of stage s + 2 are issued,
     // so the end of a stage has no staging wait and no LDS-write tail in front of the barrier
@@ -1085,21 +1353,21 @@ __device__ __forceinline__ void logit_stages(float* lds, const DecodeParams& p, 
         constexpr int MODE = decltype(mode_t)::value;
         const int sn = min(s + 1, s1 - 1);
         const float* buf = lds + ((s - s0) & 1) * STAGE64_FLOATS;
-        const float* wsg = buf + sgn * (64 * LDS_ROW);
-        const float* bsg = buf + 2 * 64 * LDS_ROW + 64 * sgn;
+        const float* wsg = buf + sgn * (Hook::bf ? BF_SIGN : 64 * LDS_ROW);
+        const float* bsg = buf + 2 * (Hook::bf ? BF_SIGN : 64 * LDS_ROW) + 64 * sgn;
         auto mid = [&]() __attribute__((always_inline)) {
 #if !(DECODE_ABLATE & 2)
             // s64 is loaded on every non-last path (at s1 - 2 the load repeats tile s1 - 1): a conditional load
             // here would make the compiler copy the 32 staging registers at every stage to merge the paths
             if constexpr (MODE == 0) {
-                stage64_store_o(lds + ((s - s0 + 1) & 1) * STAGE64_FLOATS, lsrc(sn).valid, lo, bias, s64);
+                sstore(lds + ((s - s0 + 1) & 1) * STAGE64_FLOATS, lsrc(sn).valid);
                 stage64_load_o(lsrc(min(s + 2, s1 - 1)), lo, bias, s64);
             } else if constexpr (MODE == 1) {
-                stage64_store_o(lds + ((s - s0 + 1) & 1) * STAGE64_FLOATS, lsrc(sn).valid, lo, bias, s64);
+                sstore(lds + ((s - s0 + 1) & 1) * STAGE64_FLOATS, lsrc(sn).valid);
             } else if constexpr (MODE == 2) {
                 tail();
             } else if (s + 1 < s1) {
-                stage64_store_o(lds + ((s - s0 + 1) & 1) * STAGE64_FLOATS, lsrc(sn).valid, lo, bias, s64);
+                sstore(lds + ((s - s0 + 1) & 1) * STAGE64_FLOATS, lsrc(sn).valid);
                 stage64_load_o(lsrc(min(s + 2, s1 - 1)), lo, bias, s64);
             } else {
                 tail();
@@ -1109,7 +1377,8 @@ __device__ __forceinline__ void logit_stages(float* lds, const DecodeParams& p, 
         constexpr int MID = LOGIT_MID_AT;
         if constexpr (G == 4) {
             if (sgn == 0) {
-                mfma_stage64_o<MID>(wsg, bsg, hB, lo.arow, hh, o0, o1, mid);
+                if constexpr (Hook::bf) mfma_stage64_bf<MID>(wsg, bsg, hook.Bb, lob.arowb, hh, o0, o1, mid);
+                else mfma_stage64_o<MID>(wsg, bsg, hB, lo.arow, hh, o0, o1, mid);
 #if !(DECODE_ABLATE & 1)
                 if constexpr (Hook::replaces) hook(q0, q1, s - 1);
                 else epilogue64<PAIRS>(st, q0, q1, 64 * (s - 1) + vl);
@@ -1119,7 +1388,8 @@ __device__ __forceinline__ void logit_stages(float* lds, const DecodeParams& p, 
                 if constexpr (Hook::replaces) hook(q0, q1, s - 1);
                 else epilogue64<PAIRS>(st, q0, q1, 64 * (s - 1) + vl);
 #endif
-                mfma_stage64_o<MID>(wsg, bsg, hB, lo.arow, hh, o0, o1, mid);
+                if constexpr (Hook::bf) mfma_stage64_bf<MID>(wsg, bsg, hook.Bb, lob.arowb, hh, o0, o1, mid);
+                else mfma_stage64_o<MID>(wsg, bsg, hB, lo.arow, hh, o0, o1, mid);
             }
         } else {
             const float* w1 = wsg + 32 * hf * LDS_ROW;         // this wave's 32-row tile of the stage
@@ -1186,7 +1456,7 @@ __device__ __forceinline__ uint32_t gate_row(int m) { return (uint32_t)(tile_q(m
 // One evaluate = img, then step(t) for t = -1..T. State between launches is lane-private scratch
 // plus a per-workgroup `alive` flag (nets.py:242-243 early exit).
 #define C_SLOT(s) (4u * 64u * (uint32_t)(s))            // c
-#define H_SLOT(s) (4u * 64u * (uint32_t)(64 + (s)))     // h'
+#define H_SLOT(s) (4u * 64u * (uint32_t)(64 + (s)))     // h' (H_SLOT(0) == H_SLOT_BYTES)
 #define X_SLOT(s) (4u * 64u * (uint32_t)(128 + (s)))    // x of t = 0 (img_embed)
 #define U_SLOT (4u * 64u * 192u)                        // row unfinished (1.0 / 0.0)
 
@@ -1496,9 +1766,12 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_decode_img64_kernel(DecodePar
 // logit tile, loaded during the previous step's last cell stage (PREFETCH: that load is issued)
 // SAMPLE: the sampled decode (nets.py:210-231): the logit loop stores its logits and stage sums (SampleStage), then
 // sample_pick draws each row's token with its uniform p.sample_u (fused path only)
-template <bool PAIRS, bool PREFETCH, bool SAMPLE = false, bool MUT = false>
+// SCREEN (PAIRS, greedy only): the logit loop runs in bf16 and the candidates it leaves are certified by fp32 chains
+// (ScreenStage / screen_certify above); tokens are those of the fp32 loop
+template <bool PAIRS, bool PREFETCH, bool SAMPLE = false, bool MUT = false, bool SCREEN = false>
 __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, float* lds, int t, Stage64Regs& s64,
-                                          bool& pre, float (&hB)[64], bool& hpre, const MutRes* mr = nullptr) {
+                                          bool& pre, float (&hB)[64], bool& hpre, const MutRes* mr = nullptr,
+                                          const ScreenArgs* sa = nullptr) {
     PROF_MARK(2 * (t + 1));
     const uint32_t lo = 4u * c.lane;
     const int nst = (p.V1 + 63) >> 6;
@@ -1539,6 +1812,10 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
     if (nl > 0) {
         RowState st;
         row_state_init(st);
+        float seps = 0.f;                          // SCREEN: the row's eps
+        rsrc_t scap_r = c.scr_r;                   // SCREEN: the workgroup's capture slot
+        if constexpr (SCREEN)
+            scap_r = make_rsrc(sa->cap + (size_t)c.wg * SCREEN_CAP_WORDS(p.V1), 4u * (uint32_t)SCREEN_CAP_WORDS(p.V1));
         // the cell's first gate tile does not depend on the token: its loads are issued at the last logit
         // stage's mid-point (tail) and land while the token is picked
         const bool xpre = t < p.T;
@@ -1554,6 +1831,19 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
                                  sB};
             // (no peel for the sampled decode: +2.2 %, measured)
             logit_stages<4, PAIRS, false>(lds, p, nidx, c.wave, c.sgn, 0, hB, 0, nl, st, s64, pre, tail, ss);
+        } else if constexpr (SCREEN) {
+            // eps of this row: |h|^2 from the lane's half of h and its partner's, the member's norms from the pre-kernel
+            float ssh = 0.f;
+#pragma unroll
+            for (int i = 0; i < 64; ++i) ssh += hB[i] * hB[i];
+            ssh += __shfl_xor(ssh, 32);
+            const float* nm = sa->norm + 4 * c.member;
+            seps = nn_screen_eps(nn_screen_norm(ssh), nn_screen_norm(nm[c.sgn]), nm[2 + c.sgn], sa->scale);
+            bf16x8 Bb[8];
+#pragma unroll
+            for (int i = 0; i < 64; ++i) Bb[i >> 3][i & 7] = (__bf16)hB[i];
+            const ScreenStage ss{scap_r, 4u * (uint32_t)(c.wave * 64 + lane_fresh()), 2.0f * seps + SCREEN_HU_MAX, Bb, st};
+            logit_stages<4, true, true>(lds, p, nidx, c.wave, c.sgn, 0, hB, 0, nl, st, s64, pre, tail, ss);
         } else {
             logit_stages<4, PAIRS>(lds, p, nidx, c.wave, c.sgn, 0, hB, 0, nl, st, s64, pre, tail);
         }
@@ -1563,9 +1853,11 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
         // ---- greedy token (nets.py:208-209) ------------------------------------------------
         const float m_o = __shfl_xor(st.m, 32);
         const float s_o = __shfl_xor(st.s, 32);
-        const float m = fmaxf(st.m, m_o);
-        const float stot = st.s * __builtin_amdgcn_exp2f((st.m - m) * LOG2E) + s_o * __builtin_amdgcn_exp2f((m_o - m) * LOG2E);
-        const TieWindow w = tie_window(stot, PAIRS, p.lse_margin);
+        float m = fmaxf(st.m, m_o);
+        float stot = st.s * __builtin_amdgcn_exp2f((st.m - m) * LOG2E) + s_o * __builtin_amdgcn_exp2f((m_o - m) * LOG2E);
+        // SCREEN: m and stot are over screened logits, each within eps of its exact one: lse moves by at most 2 eps
+        TieWindow w = tie_window(stot, PAIRS, SCREEN ? p.lse_margin + 2.0f * seps : p.lse_margin);
+        bool sforce = false;                     // SCREEN: this step of the workgroup is decided by the fp32 loop
         float lse = w.lse;
         int tok = 0x7fffffff;
         float lp_tok = 0.f;                      // seq_logprobs: -lse (the max, greedy) or the draw's log-prob
@@ -1590,6 +1882,55 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
                 sample_pick<false>(p, c.slog_r, vo, c.hh, mr, lse_s, R, u * T, tok, lp_tok, 120 + 24 * (t + 1));
 #endif
         } else {
+            if constexpr (SCREEN) {
+                // every id that can be in the exact window has l~ >= m~ - 2 eps - hu_out; the lane's words are within
+                // SCREEN_PACK_REL of the pair maxima they encode. A finished row's token is masked: nothing to certify
+                const float d = 2.0f * seps + w.hu_out;
+                const float thr = (m - d) - SCREEN_PACK_REL * (fabsf(m) + d);
+                const bool need = unf_prev != 0.f || p.no_mask;
+                bool bad = p.force_exact || !(fabsf(thr) < 3.0e38f) || !(w.hu_out <= SCREEN_HU_MAX) || !(stot > 0.f);
+                st.r1v = st.r0v = st.ev = NEG_INF;
+                st.r1i = st.r0i = 0x7fffffff;
+                int ncand = 0;
+                if (need && !bad)
+                    bad = !screen_certify(p, c.theta_r, c.noise_r, c.scr_r, scap_r, 4u * (uint32_t)(c.wave * 64 + lane_fresh()),
+                                          nl, c.sgn, c.hh, 4u * (uint32_t)(lane_fresh() & 31), thr, lds,
+                                          c.wave * 64 + lane_fresh(), st, ncand);
+#pragma unroll
+                for (int dd = 32; dd >= 1; dd >>= 1) ncand += __shfl_xor(ncand, dd);
+                if (ncand && lane_fresh() == 0) atomicAdd(sa->ctr, (unsigned long long)ncand);   // one atomic per wave and step
+                // The fp32 loop's token rule over the certified records, under this (wider) window: the records inside
+                // the outer window are the fp32 loop's, and a state decided here is decided the same way there. A row
+                // left undecided, over the cap or with a non-finite bound sends the workgroup's step to the fp32 loop.
+                const float mx = fmaxf(st.r1v, __shfl_xor(st.r1v, 32));
+                const float sv[4] = {st.r0v, st.r1v, __shfl_xor(st.r0v, 32), __shfl_xor(st.r1v, 32)};
+                const int si[4] = {st.r0i, st.r1i, __shfl_xor(st.r0i, 32), __shfl_xor(st.r1i, 32)};
+                int stok = 0x7fffffff;
+                bool und = win_state(st.ev, mx, w) != 0 || win_state(__shfl_xor(st.ev, 32), mx, w) != 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int ws = win_state(sv[k], mx, w);
+                    if (ws == 1 && si[k] < stok) stok = si[k];
+                    und = und || ws == 2;
+                }
+                const bool bad_o = __shfl_xor((int)bad, 32) != 0;            // the row's other lane half
+                bad = need && (bad || und || bad_o);
+                if (bad && c.hh == 0) atomicAdd(sa->ctr + 1, 1ull);
+                sforce = __syncthreads_or(bad ? 1 : 0) != 0;
+                if (!sforce) {
+                    tok = stok;
+                } else {
+                    row_state_init(st);
+                    logit_stages<4, true>(lds, p, nidx, c.wave, c.sgn, 0, hB, 0, nl, st, s64, false);
+                    cell_pre = false;            // s64 now holds logit rows: the cell loads its first tile itself
+                    const float m2 = __shfl_xor(st.m, 32), s2 = __shfl_xor(st.s, 32);
+                    m = fmaxf(st.m, m2);
+                    stot = st.s * __builtin_amdgcn_exp2f((st.m - m) * LOG2E) + s2 * __builtin_amdgcn_exp2f((m2 - m) * LOG2E);
+                    w = tie_window(stot, true, p.lse_margin);
+                    lse = w.lse;
+                }
+            }
+            if (!SCREEN || sforce) {
             const float cv[4] = {st.r0v, st.r1v, __shfl_xor(st.r0v, 32), __shfl_xor(st.r1v, 32)};
             const int ci[4] = {st.r0i, st.r1i, __shfl_xor(st.r0i, 32), __shfl_xor(st.r1i, 32)};
 #pragma unroll
@@ -1629,6 +1970,7 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
             }
             if (c.tid == 0) atomicAdd(p.stats + 0, 1);
         }
+            }
         lp_tok = -lse;                           // seq_logprobs[:, t-1] = max lp = fp32((m - m) - lse) (nets.py:208,241)
         }
         // no candidate only when every logit is NaN (torch.max would return a NaN's index):
@@ -1791,6 +2133,16 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_decode_step_kernel(DecodePara
     float hB[64];
     step_body<PAIRS, false>(p, c, lds, t, s64, pre, hB, hpre);
 }
+// the screened step (marks: 2(t + 1) .. 120 + 24(t + 1) the bf16 sweep, .. + 1 the scan, certify and token)
+__global__ __launch_bounds__(NTHREADS) void nicnes_decode_step_screen_kernel(DecodeParams p, ScreenArgs sa, int t) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const Ctx c = make_ctx(p);
+    if (t > 0 && p.alive[c.wg] == 0) return;
+    Stage64Regs s64;
+    bool pre = false, hpre = false;
+    float hB[64];
+    step_body<true, false, false, false, true>(p, c, lds, t, s64, pre, hB, hpre, nullptr, &sa);
+}
 #endif
 
 // The whole decode of a workgroup (steps t = -1 .. T) in one launch: a member's steps depend only on
@@ -1849,6 +2201,17 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_decode_steps_kernel(DecodePar
             __hip_atomic_store(p.slog_slots + slot, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+
+// the screened greedy-only decode on the fused path (step_body SCREEN; ScreenArgs)
+__global__ __launch_bounds__(NTHREADS) void nicnes_decode_steps_screen_kernel(DecodeParams p, ScreenArgs sa) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const Ctx c = make_ctx(p);
+    Stage64Regs s64;
+    bool pre = false, hpre = false;
+    float hB[64];
+    for (int t = -1; t <= p.T; ++t)
+        if (!step_body<true, true, false, false, true>(p, c, lds, t, s64, pre, hB, hpre, nullptr, &sa)) break;
 }
 
 // a mutated greedy decode on the fused path (MutHead: the embedding rows' delta' formed in step_body)
@@ -2716,11 +3079,13 @@ extern "C" hipError_t nicnes_decode_init() {
 #if DECODE_PROF
         {(const void*)nicnes_decode_step_kernel<true>, LDS64},
         {(const void*)nicnes_decode_step_kernel<false>, LDS64},
+        {(const void*)nicnes_decode_step_screen_kernel, LDS64},
 #endif
         {(const void*)nicnes_decode_img64_kernel, LDS64},
         {(const void*)nicnes_decode_steps_kernel<true>, LDS64},
         {(const void*)nicnes_decode_steps_kernel<false>, LDS64},
         {(const void*)nicnes_decode_steps_kernel<false, true>, LDS64},
+        {(const void*)nicnes_decode_steps_screen_kernel, LDS64},
         {(const void*)nicnes_decode_steps_mut_kernel<true>, LDS64},
         {(const void*)nicnes_decode_steps_mut_kernel<false>, LDS64},
         {(const void*)nicnes_decode_logit_kernel<4, true>, LDS64},
@@ -2761,7 +3126,7 @@ extern "C" hipError_t nicnes_decode_occupancy(int* coop_per_cu, int* sample_per_
                                                         NTHREADS, LDS64);
 }
 
-extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead* mh) {
+extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead* mh, ScreenArgs* sa) {
     const size_t wg0 = (size_t)m0 * (size_t)nslabs;        // workgroup index wg = member * slabs + slab
     const size_t rows = (size_t)m0 * 2 * (size_t)p->B * (size_t)p->T;
     p->noise_idx += m0;
@@ -2774,10 +3139,15 @@ extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead
     p->alive2 += wg0;
     p->part += wg0 * (size_t)p->S * PART_FLOATS;                 // part_ptr
     if (p->coop_ctr) p->coop_ctr += wg0 * COOP_CTR_STRIDE;
+    if (sa && sa->cap) {
+        sa->cap += wg0 * SCREEN_CAP_WORDS(p->V1);
+        sa->norm += 4 * (size_t)m0;
+    }
 }
 
 extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead* mh, int member_count, int nslabs,
-                                           hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch) {
+                                           hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch,
+                                           const ScreenArgs* sa) {
     const bool fused = p->G == 4 && p->S == 1;
     if (p->G != 4 && p->G != 2) return hipErrorInvalidValue;
     if (p->S < 1 || p->S > 64) return hipErrorInvalidValue;
@@ -2835,7 +3205,10 @@ extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead*
             mark(DK_STEPS);
         } else {
 #if !DECODE_PROF
-            if (mut && pairs)
+            if (!mut && pairs && sa && sa->cap && sa->norm) {
+                hipLaunchKernelGGL(nicnes_screen_norm_kernel, dim3(member_count), block, 0, stream, *p, *sa);
+                hipLaunchKernelGGL(nicnes_decode_steps_screen_kernel, grid, block, LDS64, stream, *p, *sa);
+            } else if (mut && pairs)
                 hipLaunchKernelGGL(nicnes_decode_steps_mut_kernel<true>, grid, block, LDS64, stream, *p, *mh);
             else if (mut)
                 hipLaunchKernelGGL(nicnes_decode_steps_mut_kernel<false>, grid, block, LDS64, stream, *p, *mh);
@@ -2845,8 +3218,12 @@ extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead*
                 hipLaunchKernelGGL(nicnes_decode_steps_kernel<false>, grid, block, LDS64, stream, *p);
             mark(DK_STEPS);
 #else
+            const bool scr = !mut && pairs && sa && sa->cap && sa->norm;
+            if (scr) hipLaunchKernelGGL(nicnes_screen_norm_kernel, dim3(member_count), block, 0, stream, *p, *sa);
             for (int t = -1; t <= p->T; ++t) {
-                if (pairs)
+                if (scr)
+                    hipLaunchKernelGGL(nicnes_decode_step_screen_kernel, grid, block, LDS64, stream, *p, *sa, t);
+                else if (pairs)
                     hipLaunchKernelGGL(nicnes_decode_step_kernel<true>, grid, block, LDS64, stream, *p, t);
                 else
                     hipLaunchKernelGGL(nicnes_decode_step_kernel<false>, grid, block, LDS64, stream, *p, t);
@@ -2927,6 +3304,65 @@ __global__ __launch_bounds__(256) void nicnes_lp_batch_exit_kernel(const int32_t
 extern "C" hipError_t nicnes_launch_lp_batch_exit(const int32_t* seq, float* lp, int rollouts, int B, int T,
                                                   hipStream_t stream) {
     hipLaunchKernelGGL(nicnes_lp_batch_exit_kernel, dim3(rollouts), dim3(256), 0, stream, seq, lp, B, T);
+    return hipGetLastError();
+}
+
+// ========== test entry: every logit of one (member, sign) over 32 given rows of h, computed twice ==============
+// by the 32-row fp32 MFMA tile path (stage_load / stage_store / mfma_tile, as exact_sweep runs it) and by
+// logit_chain, the function the screened decode certifies with. nicnes_test_h_scratch_kernel first lays hin [32, 128]
+// (unit order) out as one wave's H_SLOT lane scratch, as the cell's fold stores h'; both paths then read h from there,
+// the MFMA path as step_body loads its B operand. Workgroup n takes vocabulary tile n; wave 0 runs the tile's MFMA
+// chain, then the 512 threads run the tile's 32 x 32 chains, two each. Outputs [32, V1].
+__global__ __launch_bounds__(64) void nicnes_test_h_scratch_kernel(const float* hin, float* scratch) {
+    const int lane = threadIdx.x, hh = lane >> 5;
+    const rsrc_t scr_r = make_rsrc(scratch, SCR_SLOTS * 64 * 4);
+    for (int U = 0; U < 4; ++U)
+        for (int r = 0; r < 16; ++r)    // fold(): acc register r of unit block U is unit 32U + (r & 3) + 8(r >> 2) + 4hh
+            st1(scr_r, 4u * (uint32_t)lane, H_SLOT(16 * U + r), hin[(lane & 31) * 128 + 32 * U + (r & 3) + 8 * (r >> 2) + 4 * hh]);
+}
+
+__global__ __launch_bounds__(NTHREADS) void nicnes_test_logit_chain_kernel(DecodeParams p, uint64_t nidx, int sgn,
+                                                                           float* out_mfma, float* out_chain) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, n = blockIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const rsrc_t theta_r = make_rsrc(p.theta, 4u * (uint32_t)p.D);
+    const rsrc_t noise_r = make_rsrc(p.noise + nidx, 4u * (uint32_t)p.D);
+    const rsrc_t scr_r = make_rsrc(p.scratch, SCR_SLOTS * 64 * 4);
+    const rsrc_t om_r = make_rsrc(out_mfma, 4u * 32u * (uint32_t)p.V1);
+    const rsrc_t oc_r = make_rsrc(out_chain, 4u * 32u * (uint32_t)p.V1);
+    TileDesc d;
+    d.w_off = (uint32_t)p.off_log_w; d.ld = 128; d.row0 = 32 * n; d.nvalid = min(32, p.V1 - 32 * n); d.k0 = 0;
+    d.b_off = (uint32_t)p.off_log_b; d.pad_bias = NEG_INF;
+    StageRegs sr;
+    stage_load(theta_r, noise_r, d, tid, sr);
+    stage_store(lds, d, tid, sr);
+    __syncthreads();
+    if (wave == 0) {
+        float hB[64];                                            // the B operand, loaded as step_body loads it
+#pragma unroll
+        for (int i = 0; i < 64; ++i) hB[i] = ld1(scr_r, 4u * (uint32_t)lane, H_SLOT(i));
+        const f32x16 acc = mfma_tile(bias_init(lds + 2 * SIGN_FLOATS + 32 * sgn, hh), lds + sgn * SIGN_FLOATS, hB, lane);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int v = 32 * n + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            if (v < p.V1) st1(om_r, 4u * (uint32_t)((lane & 31) * p.V1 + v), 0, acc[r]);
+        }
+    }
+    const int row = tid & 31;
+#pragma unroll 1
+    for (int u = 0; u < 2; ++u) {
+        const int v = 32 * n + (tid >> 5) + 16 * u;
+        if (v < p.V1)
+            st1(oc_r, 4u * (uint32_t)(row * p.V1 + v), 0, logit_chain(p, theta_r, noise_r, v, sgn, scr_r, 4u * (uint32_t)row));
+    }
+}
+
+extern "C" hipError_t nicnes_launch_test_logit_chain(const DecodeParams* p, uint64_t nidx, int sgn, const float* hin,
+                                                     float* out_mfma, float* out_chain, hipStream_t stream) {
+    hipLaunchKernelGGL(nicnes_test_h_scratch_kernel, dim3(1), dim3(64), 0, stream, hin, p->scratch);
+    hipLaunchKernelGGL(nicnes_test_logit_chain_kernel, dim3((p->V1 + 31) / 32), dim3(NTHREADS),
+                       (size_t)STAGE_FLOATS * sizeof(float), stream, *p, nidx, sgn, out_mfma, out_chain);
     return hipGetLastError();
 }
 

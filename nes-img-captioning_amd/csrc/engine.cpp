@@ -16,11 +16,14 @@
 #include <rccl/rccl.h>
 
 #include "../../include/nicnes.h"
+#include "../../include/nicnes_math.h"
 #include "cider_kernel.h"
 #include "decode_kernel.h"
 #include "update_kernels.h"
 #include "sensitivity.h"
 
+#define SCREEN_DEFAULT 2   // the bf16-screened logit loop of the fused greedy-only decode: 0 off, 1 on,
+                           // 2 automatic: on when the decode has more workgroups than the GPU has CUs
 #define MB_RING 4   // pinned staging slots of the member -> batch map (nicnes_evaluate_batches)
 
 struct nicnes_handle {
@@ -147,6 +150,12 @@ struct nicnes_handle {
     // sent rows to the exact pass (peaked, trained-model logits put lse near binade edges); then the
     // next exact_span decodes sum the exp exactly. The fallback counter is read back asynchronously.
     int bounded_mode = 2;     // NICNES_BOUNDED_LSE: 0 never, 1 always, 2 adaptive
+    int screen_mode = SCREEN_DEFAULT;  // NICNES_SCREEN / nicnes_set_decode_screen: the fused greedy-only decode screens in bf16
+    float screen_scale = 1.0f;         // test hook NICNES_SCREEN_EPS_SCALE (>= 1)
+    uint32_t* screen_cap = nullptr;    // capture slots of screen_wgs workgroups (allocated at the first screened decode)
+    int64_t screen_wgs = 0;
+    float* screen_norm = nullptr;      // [max_members][4]
+    unsigned long long* screen_ctr = nullptr;   // [2] (ScreenArgs::ctr)
     int exact_left = 0;
     int last_bounded = 0;
     int last_decode_bounded = 0;      // nicnes_last_decode_lse: the lse mode of the last decode enqueued
@@ -257,6 +266,28 @@ bool coop_fits(const nicnes_handle* h, int G, int nslabs, int S, int count) {
 }
 
 // Buffers sized by the reference count: the cooked reference n-gram vectors (CIDEr-D).
+// the screened decode's buffers: a capture slot per workgroup of the largest fused decode and the members' norms. If
+// they cannot be had, screening is off for this engine (the fp32 loop decodes the same tokens).
+void ensure_screen(nicnes_handle* h) {
+    if (!h->screen_mode || (h->screen_cap && h->screen_norm)) return;
+    const int64_t wgs = (int64_t)h->cfg.max_members * nslabs_of(h->cfg.max_batch, 4);
+    bool ok = hipMalloc((void**)&h->screen_cap, (size_t)wgs * SCREEN_CAP_WORDS(h->V1) * sizeof(uint32_t)) == hipSuccess;
+    if (ok) ok = hipMalloc((void**)&h->screen_norm, (size_t)h->cfg.max_members * 4 * sizeof(float)) == hipSuccess;
+    if (ok && !h->screen_ctr)
+        ok = hipMalloc((void**)&h->screen_ctr, 2 * sizeof(unsigned long long)) == hipSuccess &&
+             hipMemset(h->screen_ctr, 0, 2 * sizeof(unsigned long long)) == hipSuccess;
+    if (ok) {
+        h->screen_wgs = wgs;
+        return;
+    }
+    (void)hipGetLastError();
+    if (h->screen_cap) (void)hipFree(h->screen_cap);
+    if (h->screen_norm) (void)hipFree(h->screen_norm);
+    h->screen_cap = nullptr;
+    h->screen_norm = nullptr;
+    h->screen_mode = 0;
+}
+
 int alloc_refs(nicnes_handle* h, int max_refs) {
     void* old[] = {h->ref_keys, h->ref_vec, h->ref_count, h->ref_len2, h->ref_norm};
     for (void* q : old)
@@ -386,6 +417,10 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
         if (sl && sl[0]) h->test_stall_left = atoi(sl);
         const char* ts = getenv("NICNES_TEST_SLOTS");
         if (ts && ts[0]) h->test_slots = atoi(ts);
+        const char* sc = getenv("NICNES_SCREEN");
+        if (sc && sc[0] >= '0' && sc[0] <= '2' && sc[1] == 0) h->screen_mode = sc[0] - '0';
+        const char* se = getenv("NICNES_SCREEN_EPS_SCALE");
+        if (se && se[0]) h->screen_scale = std::max(1.0f, (float)atof(se));
     }
     {
         int ncu = 0;
@@ -408,6 +443,7 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
         rc = dalloc(h, &h->rank_key, h->rank_cap);
         if (!rc) rc = dalloc(h, &h->rank_idx, h->rank_cap);
     }
+    if (!rc) ensure_screen(h);
     if (!rc) rc = alloc_refs(h, cfg->max_refs);
     if (!rc) rc = alloc_batch(h, cfg->max_batch);
     if (!rc) rc = alloc_images(h, cfg->max_batch);
@@ -441,7 +477,8 @@ int nicnes_destroy(nicnes_handle* h) {
                     h->ref_norm, h->nidx, h->seq, h->lp, h->row_scores, h->dscratch, h->stats, h->partials, h->norms,
                     h->hash_keys, h->hash_vals, h->img_hkey, h->img_hrow, h->img_vr, h->alive, h->part,
                     h->rank_key, h->rank_idx, h->mbatch, h->mut_vec, h->dbuf, h->didx, h->noise_sc, h->coop_ctr,
-                    h->zero_noise, h->zero_idx, h->sens_tok, h->su, h->base_scores, h->slog, h->slog_slots, h->zcount};
+                    h->zero_noise, h->zero_idx, h->sens_tok, h->su, h->base_scores, h->slog, h->slog_slots, h->zcount,
+                    h->screen_cap, h->screen_norm, h->screen_ctr};
     if (h->sens) nicnes_sens_destroy(h->sens);
     for (void* p : bufs)
         if (p) (void)hipFree(p);
@@ -938,6 +975,18 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     }
     if ((int64_t)count * nslabs * S > h->part_cap)
         return fail(h, NICNES_ERR_INVALID, "decode split beyond the partial-state buffer (nicnes_set_decode_split)");
+    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr};
+    // automatic: with one workgroup per CU or fewer the launch lasts as long as its slowest workgroup, and the screened
+    // decode's workgroup times spread widely (P = 256, B = 128: 23.6 ms against 22.95 ms unscreened)
+    const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)count * nslabs > h->n_cu);
+    if (screen_on && !sampled && !p.lp && bounded && G == 4 && S == 1 && !(h->mut_mode && !eval_theta)) {
+        // the screened logit loop: a capture slot per workgroup and the members' norms (ensure_screen, at create or
+        // at the setter: nothing is allocated here); a decode of more workgroups than slots runs the fp32 loop
+        if (h->screen_cap && h->screen_norm && (int64_t)count * nslabs <= h->screen_wgs) {
+            sa.cap = h->screen_cap;
+            sa.norm = h->screen_norm;
+        }
+    }
     p.G = G;
     p.S = S;
     p.part = h->part;
@@ -1002,17 +1051,18 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
             const int a = (int)((int64_t)count * i / nstr), b = (int)((int64_t)count * (i + 1) / nstr);
             DecodeParams pi = p;
             MutHead mi = mh;
-            nicnes_decode_shift(&pi, a, nslabs, &mi);
+            ScreenArgs si_ = sa;
+            nicnes_decode_shift(&pi, a, nslabs, &mi, &si_);
             hipStream_t si = i == 0 ? s : h->sx[i - 1];
             if (i > 0) HIPC(h, hipStreamWaitEvent(si, h->ev_fork, 0));
-            HIPC(h, nicnes_launch_decode(&pi, &mi, b - a, nslabs, si, nullptr, nullptr, nullptr));
+            HIPC(h, nicnes_launch_decode(&pi, &mi, b - a, nslabs, si, nullptr, nullptr, nullptr, &si_));
         }
         for (int i = 0; i < nstr - 1; ++i) {
             HIPC(h, hipEventRecord(h->ev_join[i], h->sx[i]));
             HIPC(h, hipStreamWaitEvent(s, h->ev_join[i], 0));
         }
     } else {
-        HIPC(h, nicnes_launch_decode(&p, &mh, count, nslabs, s, h->timing ? h->dev : nullptr, h->dev_kind, &n_ev));
+        HIPC(h, nicnes_launch_decode(&p, &mh, count, nslabs, s, h->timing ? h->dev : nullptr, h->dev_kind, &n_ev, &sa));
     }
     h->n_dev = h->timing ? n_ev : 0;
     h->multi_stream = nstr > 1;
@@ -1297,6 +1347,24 @@ int nicnes_stats(nicnes_handle* h, int64_t* out4_host) {
     return NICNES_OK;
 }
 
+int nicnes_screen_stats(nicnes_handle* h, int64_t* out2_host) {
+    if (!h || !out2_host) return NICNES_ERR_INVALID;
+    unsigned long long st[2] = {0, 0};
+    HIPC(h, hipSetDevice(h->device));
+    if (h->screen_ctr) HIPC(h, hipMemcpy(st, h->screen_ctr, sizeof st, hipMemcpyDeviceToHost));
+    out2_host[0] = (int64_t)st[0];
+    out2_host[1] = (int64_t)st[1];
+    return NICNES_OK;
+}
+
+int nicnes_set_decode_screen(nicnes_handle* h, int32_t mode) {
+    if (!h || mode < 0 || mode > 2) return NICNES_ERR_INVALID;
+    HIPC(h, hipSetDevice(h->device));
+    h->screen_mode = mode;
+    ensure_screen(h);
+    return NICNES_OK;
+}
+
 int nicnes_set_timing(nicnes_handle* h, int on) {
     if (!h) return NICNES_ERR_INVALID;
     HIPC(h, hipSetDevice(h->device));
@@ -1368,6 +1436,37 @@ int nicnes_set_decode_coop(nicnes_handle* h, int32_t mode) {
 int nicnes_last_decode_lse(nicnes_handle* h, int32_t* bounded_host) {
     if (!h || !bounded_host) return NICNES_ERR_INVALID;
     *bounded_host = h->last_decode_bounded;
+    return NICNES_OK;
+}
+
+int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
+                            const float* h_rows, float* out_mfma, float* out_chain, void* stream) {
+    if (!h || !h_rows || !out_mfma || !out_chain || member < 0 || (sign != 0 && sign != 1)) return NICNES_ERR_INVALID;
+    if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
+    if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
+    if (h->mut_mode) return fail(h, NICNES_ERR_UNSUPPORTED, "nicnes_test_logit_chain: plain mutations only");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    if (!h->noise_sc) {
+        HIPC(h, hipDeviceSynchronize());
+        int rc = dalloc(h, &h->noise_sc, (size_t)h->cfg.noise_len);
+        if (rc) return rc;
+    }
+    if (!h->sc_valid || __builtin_bit_cast(uint32_t, h->sc_sigma) != __builtin_bit_cast(uint32_t, sigma)) {
+        HIPC(h, nicnes_launch_scale(h->noise, h->noise_sc, h->cfg.noise_len, sigma, s));
+        h->sc_sigma = sigma;
+        h->sc_valid = true;
+    }
+    DecodeParams p{};
+    p.theta = h->theta32;
+    p.noise = h->noise_sc;
+    p.V1 = h->V1;
+    p.D = h->D;
+    p.off_log_w = h->off[3];
+    p.off_log_b = h->off[4];
+    p.scratch = h->dscratch;        // one wave's lane scratch holds the rows of h (no decode runs beside this)
+    const uint64_t nidx = nn_noise_index(h->cfg.noise_seed, iteration, (uint64_t)member, h->cfg.noise_len, (uint64_t)h->D);
+    HIPC(h, nicnes_launch_test_logit_chain(&p, nidx, sign, h_rows, out_mfma, out_chain, s));
     return NICNES_OK;
 }
 

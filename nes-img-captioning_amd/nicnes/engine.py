@@ -402,6 +402,26 @@ class Engine:
         check(self.L.nicnes_last_decode_lse(self.h, ctypes.byref(out)), self.h, 'last_decode_lse')
         return bool(out.value)
 
+    def set_decode_screen(self, on):
+        """The bf16-screened logit loop of the fused greedy-only decode on (True), off (False) or 'auto' (the default:
+        on when members x slabs exceed the CU count). Tokens do not depend on it."""
+        mode = 2 if (isinstance(on, str) and on == 'auto') else int(bool(on))
+        check(self.L.nicnes_set_decode_screen(self.h, mode), self.h, 'set_decode_screen')
+
+    def test_logit_chain(self, iteration, member, sigma, sign, h_rows):
+        """Test entry: the logits of one (member, sign) over h_rows [32, 128] by the exact pass's MFMA tile path and by
+        the fmaf chain in the MFMA's k order; two [32, vocab_size + 1] fp32 tensors, equal bit for bit."""
+        hr = torch.as_tensor(h_rows, dtype=torch.float32, device=self.device).contiguous()
+        assert hr.shape == (32, self.cfg.rnn_size)
+        om = torch.empty((32, self.cfg.vocab_size + 1), dtype=torch.float32, device=self.device)
+        oc = torch.empty_like(om)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_test_logit_chain(self.h, ctypes.c_uint64(iteration), int(member), ctypes.c_float(sigma),
+                                                 int(sign), _ptr(hr), _ptr(om), _ptr(oc), self._stream()), self.h,
+                  'test_logit_chain')
+            torch.cuda.current_stream().synchronize()   # hr stays alive until the kernel has read it
+        return om, oc
+
     def decode_path(self, B=None, count=1):
         """'fused', 'split' or 'coop': the decode path an evaluate of `count` members would take."""
         out = ctypes.c_int32()
@@ -463,5 +483,7 @@ class Engine:
     def stats(self):
         out = (ctypes.c_int64 * 4)()
         check(self.L.nicnes_stats(self.h, out), self.h, 'stats')
+        sc = (ctypes.c_int64 * 2)()
+        check(self.L.nicnes_screen_stats(self.h, sc), self.h, 'screen_stats')
         return {'tie_fallbacks': out[0], 'sample_stage_fallbacks': out[1], 'coop_timeouts': out[2],
-                'sample_slot_timeouts': out[3]}
+                'sample_slot_timeouts': out[3], 'screen_candidates': sc[0], 'screen_fallback_rows': sc[1]}
