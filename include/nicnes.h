@@ -347,6 +347,22 @@ int nicnes_screen_stats(nicnes_handle* h, int64_t* out2_host);
  * only. Asynchronous on stream. */
 int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
                             const float* h_rows_dev, float* out_mfma_dev, float* out_chain_dev, void* stream);
+/* Test entry (no reference counterpart): the scorer of nicnes_evaluate* on GIVEN token rows instead of a decode's, so a
+ * test can choose the hypotheses (caption lengths, repeats, ids at the key packing's top bit) that a decode of a random
+ * theta never emits. seq_dev [n_cand, rows, seq_length] int32; candidates 2k and 2k + 1 are member k's, scored on batch
+ * member_batch_host[k] (HOST, n_cand / 2 entries, copied; NULL = the one batch held; needs an even n_cand);
+ * lp_dev [n_cand, rows, seq_length] fp32 (nullable: the criteria modes then give the mean form, as an evaluate without
+ * log-probs cannot; the criteria stop a row's mask at its first 0, so rows given with log-probs are 0 from their first
+ * 0 on, as a decode's are); base_dev [n_cand, rows / rpi] fp64 (nullable) = the self-critical modes' greedy row scores.
+ * scores_out_dev [n_cand, rows] fp64 = every row's CIDEr-D, fitness_out_dev [n_cand] fp64 = the fitness of the handle's
+ * current mode. Uses the handle's fitness mode, rows-per-image setting (rows must be B * rpi; rpi = 1 in the greedy
+ * modes), held batches and df table; needs no theta and no noise table. It runs the dispatch the evaluates end with
+ * (image tables when every image has <= 8 references, else the per-reference scan). NICNES_ERR_INVALID: no batch set,
+ * rows != B * rpi, n_cand outside [1, 2 * max_members] (the row-score scratch), member_batch with an odd n_cand or an
+ * entry outside [0, n_batches). Asynchronous on stream. */
+int nicnes_test_score_rows(nicnes_handle* h, const int32_t* seq_dev, int32_t n_cand, int32_t rows,
+                           const int32_t* member_batch_host, const float* lp_dev, const double* base_dev,
+                           double* scores_out_dev, double* fitness_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

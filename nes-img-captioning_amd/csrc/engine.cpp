@@ -793,6 +793,59 @@ int nicnes_evaluate_lp(nicnes_handle* h, uint64_t iteration, int32_t member_begi
                                    stream);
 }
 
+// The row buffers (tokens, log-probs, row scores, decode scratch) grown to `rows` rollout rows, before anything
+// takes their addresses.
+static int ensure_rows(nicnes_handle* h, int rows) {
+    if (rows <= h->cfg.max_batch) return NICNES_OK;
+    HIPC(h, hipDeviceSynchronize());
+    return alloc_batch(h, rows);
+}
+
+// The caller's member -> batch map (host, `count` entries, nullable) checked and copied to the device on s:
+// *mb_out = the device map, or NULL when none was given (then only one batch may be held).
+static int stage_member_batch(nicnes_handle* h, const int32_t* member_batch_host, int count, hipStream_t s,
+                              const int32_t** mb_out) {
+    *mb_out = nullptr;
+    if (member_batch_host) {
+        for (int k = 0; k < count; ++k)
+            if (member_batch_host[k] < 0 || member_batch_host[k] >= h->n_batches)
+                return fail(h, NICNES_ERR_INVALID, "member_batch entry outside [0, n_batches)");
+        // the caller's array may go away on return: copied to a pinned ring slot whose previous copy has run
+        const int slot = h->mb_next;
+        h->mb_next = (slot + 1) % MB_RING;
+        if (h->mb_used[slot]) HIPC(h, hipEventSynchronize(h->mb_ev[slot]));
+        std::memcpy(h->mb_pin[slot], member_batch_host, (size_t)count * sizeof(int32_t));
+        HIPC(h, hipMemcpyAsync(h->mbatch, h->mb_pin[slot], (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPC(h, hipEventRecord(h->mb_ev[slot], s));
+        h->mb_used[slot] = true;
+        *mb_out = h->mbatch;
+    } else if (h->n_batches != 1) {
+        return fail(h, NICNES_ERR_INVALID, "several batches are held: pass member_batch (nicnes_evaluate_batches)");
+    }
+    return NICNES_OK;
+}
+
+// CIDEr-D of n_cand candidates of `rows` rollout rows each (seq, lp [n_cand, rows, T] on the device; lp, mb, base
+// and scores_out nullable) against the batches held, and the fitness of the handle's mode: the image tables when
+// every image has <= IMG_MAXR references (per-row scores land in h->row_scores), else the per-reference scan.
+// The one scorer dispatch: nicnes_evaluate* and nicnes_test_score_rows both end here.
+static int score_rollouts(nicnes_handle* h, const int32_t* seq, const float* lp, int n_cand, int rows, int rpi,
+                          const int32_t* mb, const double* base, double* fitness_out, double* scores_out,
+                          hipStream_t s) {
+    CiderTables tb = tables_of(h);
+    if (h->img_tables) {
+        HIPC(h, nicnes_launch_cider_img(seq, n_cand, rows, h->cfg.seq_length, &tb, h->img_ref_start, mb, lp,
+                                         h->fitness_mode, h->row_scores, fitness_out, s, base, rpi));
+        if (scores_out)
+            HIPC(h, hipMemcpyAsync(scores_out, h->row_scores, (size_t)n_cand * rows * sizeof(double),
+                                   hipMemcpyDeviceToDevice, s));
+    } else {
+        HIPC(h, nicnes_launch_cider(seq, n_cand, rows, h->cfg.seq_length, &tb, h->img_ref_start, mb, lp,
+                                    h->fitness_mode, fitness_out, s, base, scores_out, rpi));
+    }
+    return NICNES_OK;
+}
+
 // eval_theta: the sigma = 0 rollout of theta itself (count 1), decoded ONCE: sign + takes the first half of the
 // batch's images and sign - the second (at sigma = 0 both signs are theta, so the halves are one decode of the
 // batch), scored as one rollout of B rows
@@ -833,28 +886,9 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     // the row buffers grow before anything below takes their addresses
     const int rpi = sampled ? h->rpi : 1;
     const int rows_total = h->B * rpi;
-    if (rows_total > h->cfg.max_batch) {
-        HIPC(h, hipDeviceSynchronize());
-        int rc = alloc_batch(h, rows_total);
-        if (rc) return rc;
-    }
+    if (int rc = ensure_rows(h, rows_total)) return rc;
     const int32_t* mb = nullptr;
-    if (member_batch_host) {
-        for (int k = 0; k < count; ++k)
-            if (member_batch_host[k] < 0 || member_batch_host[k] >= h->n_batches)
-                return fail(h, NICNES_ERR_INVALID, "member_batch entry outside [0, n_batches)");
-        // the caller's array may go away on return: copied to a pinned ring slot whose previous copy has run
-        const int slot = h->mb_next;
-        h->mb_next = (slot + 1) % MB_RING;
-        if (h->mb_used[slot]) HIPC(h, hipEventSynchronize(h->mb_ev[slot]));
-        std::memcpy(h->mb_pin[slot], member_batch_host, (size_t)count * sizeof(int32_t));
-        HIPC(h, hipMemcpyAsync(h->mbatch, h->mb_pin[slot], (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIPC(h, hipEventRecord(h->mb_ev[slot], s));
-        h->mb_used[slot] = true;
-        mb = h->mbatch;
-    } else if (h->n_batches != 1) {
-        return fail(h, NICNES_ERR_INVALID, "several batches are held: pass member_batch (nicnes_evaluate_batches)");
-    }
+    if (int rc = stage_member_batch(h, member_batch_host, count, s, &mb)) return rc;
     DecodeParams p;
     p.theta = h->theta32;
     p.noise = h->noise;
@@ -1075,19 +1109,9 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
         h->stats_pending = true;
         h->last_bounded = bounded && !p.lp;
     }
-    CiderTables tb = tables_of(h);
     const int n_cand = eval_theta ? 1 : 2 * count;      // eval_theta: rows s * half + b = image s * half + b
     const double* base = self_critical ? h->base_scores : nullptr;
-    if (h->img_tables) {
-        HIPC(h, nicnes_launch_cider_img(p.seq, n_cand, rows_total, h->cfg.seq_length, &tb, h->img_ref_start, mb, p.lp,
-                                         h->fitness_mode, h->row_scores, fitness_out, s, base, rpi));
-        if (scores_out)
-            HIPC(h, hipMemcpyAsync(scores_out, h->row_scores, (size_t)n_cand * rows_total * sizeof(double),
-                                   hipMemcpyDeviceToDevice, s));
-    } else {
-        HIPC(h, nicnes_launch_cider(p.seq, n_cand, rows_total, h->cfg.seq_length, &tb, h->img_ref_start, mb, p.lp,
-                                    h->fitness_mode, fitness_out, s, base, scores_out, rpi));
-    }
+    if (int rc = score_rollouts(h, p.seq, p.lp, n_cand, rows_total, rpi, mb, base, fitness_out, scores_out, s)) return rc;
     if (h->timing) HIPC(h, hipEventRecord(h->ev[2], s));
     return NICNES_OK;
 }
@@ -1468,6 +1492,26 @@ int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member
     const uint64_t nidx = nn_noise_index(h->cfg.noise_seed, iteration, (uint64_t)member, h->cfg.noise_len, (uint64_t)h->D);
     HIPC(h, nicnes_launch_test_logit_chain(&p, nidx, sign, h_rows, out_mfma, out_chain, s));
     return NICNES_OK;
+}
+
+int nicnes_test_score_rows(nicnes_handle* h, const int32_t* seq, int32_t n_cand, int32_t rows,
+                           const int32_t* member_batch_host, const float* lp, const double* base, double* scores_out,
+                           double* fitness_out, void* stream) {
+    if (!h || !seq || !scores_out || !fitness_out) return NICNES_ERR_INVALID;
+    if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
+    const int rpi = h->fitness_mode >= NICNES_FITNESS_SAMPLE ? h->rpi : 1;
+    if (rows != h->B * rpi) return fail(h, NICNES_ERR_INVALID, "rows must be B * rows_per_image (B in the greedy modes)");
+    // h->row_scores holds [2 * max_members, rows] and h->mbatch [max_members] (the evaluate's 2 * count candidates)
+    if (n_cand < 1 || n_cand > 2 * h->cfg.max_members)
+        return fail(h, NICNES_ERR_INVALID, "n_cand out of [1, 2 * max_members]");
+    if (member_batch_host && (n_cand & 1))
+        return fail(h, NICNES_ERR_INVALID, "member_batch maps members: n_cand must be even (two candidates each)");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    if (int rc = ensure_rows(h, rows)) return rc;
+    const int32_t* mb = nullptr;
+    if (int rc = stage_member_batch(h, member_batch_host, n_cand / 2, s, &mb)) return rc;
+    return score_rollouts(h, seq, lp, n_cand, rows, rpi, mb, base, fitness_out, scores_out, s);
 }
 
 int nicnes_decode_path(nicnes_handle* h, int32_t B, int32_t count, int32_t* out_host) {

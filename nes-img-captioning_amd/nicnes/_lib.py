@@ -23,7 +23,7 @@ EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_create', 'nicne
            'nicnes_set_mutation_proportional', 'nicnes_theta_zeros',
            'nicnes_set_decode_coop', 'nicnes_decode_path', 'nicnes_sum_sensitivity', 'nicnes_grad_partial_range',
            'nicnes_evaluate_theta', 'nicnes_set_sample_draws', 'nicnes_set_rows_per_image',
-           'nicnes_last_decode_lse', 'nicnes_test_logit_chain',
+           'nicnes_last_decode_lse', 'nicnes_test_logit_chain', 'nicnes_test_score_rows',
            'nicnes_set_decode_screen', 'nicnes_screen_stats']
 
 
@@ -102,6 +102,7 @@ def lib(path=None):
         'nicnes_set_decode_screen': (c.c_int, [vp, i32]),
         'nicnes_screen_stats': (c.c_int, [vp, vp]),
         'nicnes_test_logit_chain': (c.c_int, [vp, u64, i32, f32, i32, vp, vp, vp, vp]),
+        'nicnes_test_score_rows': (c.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
         'nicnes_sum_sensitivity': (c.c_int, [vp, i32, f32, vp, vp]),
         'nicnes_comm_unique_id': (c.c_int, [vp]),
         'nicnes_comm_init': (c.c_int, [vp, i32, i32, vp]),

@@ -155,8 +155,13 @@ class Engine:
         B = fcs[0].shape[0]
         if any(f.shape[0] != B for f in fcs):
             raise ValueError('batches must have the same number of images')
+        refs_np = np.concatenate(rows, 0)
+        # the scorer packs a token id into 14 bits of the n-gram key: an id outside the vocabulary would alias another word
+        if refs_np.size and (refs_np.min() < 0 or refs_np.max() > self.cfg.vocab_size):
+            raise ValueError('reference token outside [0, vocab_size = %d]: min %d, max %d'
+                             % (self.cfg.vocab_size, refs_np.min(), refs_np.max()))
         fc_t = self._dev(np.concatenate(fcs, 0), torch.float32)
-        refs = self._dev(np.concatenate(rows, 0), torch.int32)
+        refs = self._dev(refs_np, torch.int32)
         starts = self._dev(np.array(start, np.int32), torch.int32)
         self._keep['fc'], self._keep['refs'], self._keep['ref_start'] = fc_t, refs, starts
         with torch.cuda.device(self.device):
@@ -421,6 +426,36 @@ class Engine:
                   'test_logit_chain')
             torch.cuda.current_stream().synchronize()   # hr stays alive until the kernel has read it
         return om, oc
+
+    def test_score_rows(self, seq, member_batch=None, lp=None, base=None):
+        """Test entry: the evaluate's scorer on given token rows. seq [n_cand, rows, seq_length] int; member_batch
+        (n_cand / 2 batch indices), lp [n_cand, rows, seq_length] fp32 and base [n_cand, rows / rows_per_image] fp64
+        are optional. Uses the fitness mode, rows per image, batches and df table the handle holds. Returns
+        (scores [n_cand, rows], fitness [n_cand]), fp64 tensors on the GPU (synchronises)."""
+        sq = self._dev(seq, torch.int32)
+        if sq.dim() != 3 or sq.shape[2] != self.cfg.seq_length:
+            raise ValueError('seq must be [n_cand, rows, seq_length]')
+        n_cand, rows = int(sq.shape[0]), int(sq.shape[1])
+        lp_t = self._dev(lp, torch.float32) if lp is not None else None
+        if lp_t is not None and lp_t.shape != sq.shape:
+            raise ValueError('lp must have the shape of seq')
+        base_t = self._dev(base, torch.float64) if base is not None else None
+        if base_t is not None and (base_t.dim() != 2 or base_t.shape[0] != n_cand or base_t.shape[1] < 1 or
+                                   rows % base_t.shape[1]):
+            raise ValueError('base must be [n_cand, rows / rows_per_image]')
+        mb = None
+        if member_batch is not None:
+            mb_np = np.ascontiguousarray(np.asarray(member_batch, np.int32))
+            if mb_np.ndim != 1 or mb_np.shape[0] < n_cand // 2:
+                raise ValueError('member_batch needs one entry per member (two candidates each)')
+            mb = mb_np.ctypes.data_as(ctypes.c_void_p)
+        scores = torch.empty((n_cand, rows), dtype=torch.float64, device=self.device)
+        fit = torch.empty(n_cand, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_test_score_rows(self.h, _ptr(sq), n_cand, rows, mb, _ptr(lp_t), _ptr(base_t),
+                                                _ptr(scores), _ptr(fit), self._stream()), self.h, 'test_score_rows')
+            torch.cuda.current_stream().synchronize()   # the inputs stay alive until the kernels have read them
+        return scores, fit
 
     def decode_path(self, B=None, count=1):
         """'fused', 'split' or 'coop': the decode path an evaluate of `count` members would take."""
