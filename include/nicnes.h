@@ -191,6 +191,47 @@ int nicnes_evaluate_batches(nicnes_handle* h, uint64_t iteration, int32_t member
 int nicnes_evaluate_theta(nicnes_handle* h, int32_t batch, uint64_t iteration, double* fitness_out, int32_t* seq_out,
                           float* logprob_out, void* stream);
 
+/* A resident evaluation split: the images a validation score is computed on (CaptPolicy.accuracy_on -> eval_split,
+ * src/captioning/policies.py:130-143, src/captioning/eval_utils.py:110-180: a greedy decode of theta on the first
+ * num_val_items images of a split, one row per image, scored by COCOEvalCap, eval_utils.py:60-107). Owned by the
+ * handle (destroyed with it), and separate from everything the evaluates use: the training batches, the handle's df
+ * table, the fitness mode, the mutation, rows_per_image and the sampled draws are neither read nor changed by the
+ * nicnes_split_* calls.
+ * nicnes_split_create copies its arrays before it returns (synchronising; each may be a host or a device pointer):
+ * fc [N, F] fp32; ref_tokens [n_refs, seq_length] and img_ref_start [N + 1] in the layout of nicnes_set_batch;
+ * the split's OWN document-frequency table in the layout of nicnes_set_df_table (COCOEvalCap's Cider takes its df
+ * from the evaluated split's references, ref_len_log = log(N) then). n_refs = 0 makes a decode-only split (images
+ * without references: nicnes_split_score / _evaluate return NICNES_ERR_INVALID on it). */
+typedef struct nicnes_split nicnes_split;
+int nicnes_split_create(nicnes_handle* h, const float* fc, int32_t N, const int32_t* ref_tokens, int32_t n_refs,
+                        const int32_t* img_ref_start, const uint64_t* df_keys, const double* df, int64_t n_df,
+                        double ref_len_log, nicnes_split** out, void* stream);
+int nicnes_split_destroy(nicnes_handle* h, nicnes_split* split);
+/* Greedy tokens of the handle's current theta itself (no mutation applies, no noise table is needed, as
+ * nicnes_evaluate_theta) on images [first, first + count) of the split, any count in [1, N], in ONE enqueue: the
+ * range's slabs are the halves of ceil(count / 256) pseudo-members over the zero noise slice, on the decode path
+ * (fused / split / coop) the engine's shape rule picks for that many workgroups; the tail's rows are decoded and
+ * dropped. seq_out [count, seq_length] int32: bit for bit nicnes_evaluate_theta's rows of the same images, whatever
+ * the shape. logprob_out (nullable) [count, seq_length] fp32: the log-prob of every token up to and including the
+ * row's end token and 0 after it (nicnes_evaluate_theta's rows also keep the later steps their batch still ran,
+ * which depend on the batch's other rows). The work buffers grow with the largest range decoded (synchronising
+ * then); more than 2^20 images in one range is NICNES_ERR_INVALID. */
+int nicnes_split_decode(nicnes_handle* h, nicnes_split* split, int32_t first, int32_t count, int32_t* seq_out,
+                        float* logprob_out, void* stream);
+/* COCOEvalCap's java-free metrics of GIVEN token rows seq_dev [count, seq_length] as the captions of images
+ * [first, first + count): a caption is its tokens before the first 0 (decode_sequence, eval_utils.py:13-27), the
+ * references likewise; an empty caption scores 0 and has length 0. metrics_out_dev [6] fp64 = Bleu_1..4 (corpus
+ * level, pycocoevalcap bleu_scorer with option 'closest'), ROUGE_L (mean over images, beta = 1.2), CIDEr (mean
+ * CIDEr-D over images on the reference's scale, sigma = 6, the split's df table; no x 100). totals_out_dev [10]
+ * int64 = the BLEU statistics correct[1..4], guess[1..4], testlen, reflen. row_cider_out_dev (nullable) [count]
+ * fp64 = every image's CIDEr-D. Sums run in a fixed order (no floating atomics): the same bits on every run. On a
+ * handle with a contained decode fault (nicnes_stats) the six metrics are NaN, as the fitness is. */
+int nicnes_split_score(nicnes_handle* h, nicnes_split* split, int32_t first, int32_t count, const int32_t* seq_dev,
+                       int64_t* totals_out_dev, double* metrics_out_dev, double* row_cider_out_dev, void* stream);
+/* nicnes_split_decode + nicnes_split_score of its tokens; seq_out (nullable) [count, seq_length] receives them. */
+int nicnes_split_evaluate(nicnes_handle* h, nicnes_split* split, int32_t first, int32_t count, int64_t* totals_out_dev,
+                          double* metrics_out_dev, double* row_cider_out_dev, int32_t* seq_out, void* stream);
+
 /* Centred ranks + antithetic weights over the WHOLE population, replaces
  * NESMaster.compute_centered_ranks and the weights line of gradient_estimate
  * (src/algorithm/nic_nes/nic_nes_master.py:170-205). fitness [P, 2] fp64 -> cr [P, 2] (or NULL),

@@ -38,8 +38,9 @@ __device__ __forceinline__ bool decode_fault(const int32_t* f) {
 extern "C" uint64_t nicnes_df_hash_capacity(int64_t n);
 extern "C" hipError_t nicnes_launch_df_hash_build(const uint64_t* keys, const double* vals, int64_t n, uint64_t* hkeys,
                                                   double* hvals, uint64_t mask, hipStream_t stream);
+// words = 1: the references without their end token (the validation scorer), 0: array_to_str's strings
 extern "C" hipError_t nicnes_launch_cook_refs(const int32_t* ref_tokens, int n_refs, int T, const CiderTables* tb,
-                                              hipStream_t stream);
+                                              hipStream_t stream, int words = 0);
 extern "C" hipError_t nicnes_launch_img_ngrams(const int32_t* img_ref_start, int B, const CiderTables* tb,
                                                hipStream_t stream);
 // lp (nullable) [n_cand, B, T] per-step log-probs; crit = fitness criterion (nicnes_set_fitness_mode)
@@ -57,3 +58,11 @@ extern "C" hipError_t nicnes_launch_cider(const int32_t* seq, int n_cand, int B,
                                           const int32_t* img_ref_start, const int32_t* member_batch, const float* lp,
                                           int crit, double* fitness_out, hipStream_t stream, const double* base = nullptr,
                                           double* scores = nullptr, int rpi = 1);
+// The validation metrics of `count` hypothesis rows seq [count, T] against images [first, first + count) of a split
+// (references cooked with words = 1): img_stats [count, 10] int32, img_rouge / img_cider [count] fp64 per image
+// (scratch and output), totals_out [10] int64, metrics_out [6] fp64 (Bleu_1..4, ROUGE_L, CIDEr). nicnes.h:
+// nicnes_split_score.
+extern "C" hipError_t nicnes_launch_split_metrics(const int32_t* seq, int first, int count, int T, const CiderTables* tb,
+                                                  const int32_t* img_ref_start, const int32_t* ref_tokens,
+                                                  int32_t* img_stats, double* img_rouge, double* img_cider,
+                                                  int64_t* totals_out, double* metrics_out, hipStream_t stream);

@@ -115,26 +115,42 @@ __device__ __forceinline__ void ngram_key(const int32_t* row, int T, int lane, i
     g.vec = 0.0;
 }
 
-// ... and its weight
-__device__ __forceinline__ NgramLane ngram_lane(const int32_t* row, int T, int lane, const CiderTables& tb) {
+// ... and its weight (L: the caption's length in tokens; tf_out (nullable): the n-gram's count over the row)
+__device__ __forceinline__ NgramLane ngram_lane(const int32_t* row, int T, int lane, int L, const CiderTables& tb,
+                                                int* tf_out = nullptr) {
     NgramLane g;
     int tf;
-    ngram_key(row, T, lane, caption_len(row, T), g, tf);
+    ngram_key(row, T, lane, L, g, tf);
     if (g.first) {
         const double df = df_lookup(tb, g.key);
         g.vec = (double)tf * (tb.ref_len - log(df > 1.0 ? df : 1.0));
     }
+    if (tf_out) *tf_out = tf;
     return g;
 }
 
+__device__ __forceinline__ NgramLane ngram_lane(const int32_t* row, int T, int lane, const CiderTables& tb) {
+    return ngram_lane(row, T, lane, caption_len(row, T), tb);
+}
+
+// words of decode_sequence(row) (captioning/eval_utils.py:13-27): the tokens before the first 0
+__device__ __forceinline__ int word_len(const int32_t* row, int T) {
+    int L = T;
+    for (int k = T - 1; k >= 0; --k) if (row[k] == 0) L = k;
+    return L;
+}
+
 // ---- per-batch reference vectors --------------------------------------------------------------
+// WORDS: the reference is its words without the end token (the validation scorer, COCOEvalCap's strings); else
+// array_to_str's string with the 0 (the fitness scorer)
+template <bool WORDS>
 __global__ __launch_bounds__(256) void nicnes_cook_refs_kernel(const int32_t* ref_tokens, int n_refs, int T,
                                                                CiderTables tb) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= n_refs) return;
     const int32_t* row = ref_tokens + (size_t)r * T;
-    const NgramLane g = ngram_lane(row, T, lane, tb);
+    const NgramLane g = ngram_lane(row, T, lane, WORDS ? word_len(row, T) : caption_len(row, T), tb);
     const uint64_t firsts = __ballot(g.first);
     const int rank = __popcll(firsts & ((1ull << lane) - 1ull));
     if (g.first) {
@@ -145,7 +161,7 @@ __global__ __launch_bounds__(256) void nicnes_cook_refs_kernel(const int32_t* re
     if ((lane & 15) == 0) tb.ref_norm[(size_t)r * 4 + (lane >> 4)] = nrm;
     if (lane == 0) {
         tb.ref_count[r] = __popcll(firsts);
-        const int L = caption_len(row, T);
+        const int L = WORDS ? word_len(row, T) : caption_len(row, T);
         tb.ref_len2[r] = L > 1 ? L - 1 : 0;          // bigram count (counts2vec 'length' quirk)
     }
 }
@@ -274,9 +290,14 @@ extern "C" hipError_t nicnes_launch_df_hash_build(const uint64_t* keys, const do
 }
 
 extern "C" hipError_t nicnes_launch_cook_refs(const int32_t* ref_tokens, int n_refs, int T, const CiderTables* tb,
-                                              hipStream_t stream) {
+                                              hipStream_t stream, int words) {
     if (n_refs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(nicnes_cook_refs_kernel, dim3((n_refs + 3) / 4), dim3(256), 0, stream, ref_tokens, n_refs, T, *tb);
+    if (words)
+        hipLaunchKernelGGL(nicnes_cook_refs_kernel<true>, dim3((n_refs + 3) / 4), dim3(256), 0, stream, ref_tokens, n_refs,
+                           T, *tb);
+    else
+        hipLaunchKernelGGL(nicnes_cook_refs_kernel<false>, dim3((n_refs + 3) / 4), dim3(256), 0, stream, ref_tokens, n_refs,
+                           T, *tb);
     return hipGetLastError();
 }
 
@@ -478,5 +499,175 @@ extern "C" hipError_t nicnes_launch_cider_img(const int32_t* seq, int n_cand, in
                        stream, seq, B, T, *tb, img_ref_start, member_batch, scores, rpi, rows_wg);
     hipLaunchKernelGGL(nicnes_cider_finish_kernel, dim3(n_cand), dim3(256), 0, stream, seq, B, T, (const double*)scores,
                        lp, crit, fitness_out, base, rpi, tb->fault);
+    return hipGetLastError();
+}
+
+// ========== validation-split metrics (nicnes_split_score): COCOEvalCap's java-free scorers on token rows ==========
+// Replaces the Bleu / Rouge / Cider scorers of language_eval (captioning/eval_utils.py:60-107) on the strings of
+// decode_sequence (:13-27): a caption is its tokens BEFORE the first 0, so an n-gram never holds the end token (the
+// fitness scorer above scores array_to_str strings, which do). One wave per image; lane j owns n-gram slot j & 15 of
+// size (j >> 4) + 1 as above. Per image:
+//   CIDEr-D  the per-reference scan of nicnes_cider_kernel (any number of references), on references cooked by
+//            nicnes_cook_refs_kernel<true> with the split's own df table
+//   BLEU     bleu_scorer's statistics with option 'closest': correct[n] = sum over the distinct n-grams of
+//            min(count_hyp, max over refs count_ref), guess[n] = max(0, testlen - n + 1), reflen = the reference
+//            length minimising (|l - testlen|, l); integers, summed over the corpus by the finish kernel
+//   ROUGE_L  rouge.py: P = max_r lcs / |hyp|, R = max_r lcs / |ref_r|, beta = 1.2; lane r takes reference r, the LCS
+//            by the bit-vector recurrence V' = (V + (V & M)) | (V & ~M) over the hypothesis' <= 16 positions
+// An empty hypothesis scores 0 in all three and adds length 0.
+#define MET_STATS 10   // correct[1..4], guess[1..4], testlen, reflen
+
+__global__ __launch_bounds__(256) void nicnes_split_metrics_kernel(const int32_t* seq, int first, int count, int T,
+                                                                   CiderTables tb, const int32_t* img_ref_start,
+                                                                   const int32_t* ref_tokens, int32_t* img_stats,
+                                                                   double* img_rouge, double* img_cider) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 4 + wave;
+    if (i >= count) return;                                   // (the whole wave)
+    const int32_t* row = seq + (size_t)i * T;
+    const int Lh = word_len(row, T);
+    int tf;
+    const NgramLane g = ngram_lane(row, T, lane, Lh, tb, &tf);
+    const double nh = sqrt(seg_sum(g.first ? g.vec * g.vec : 0.0));
+    const int len_h = Lh > 1 ? Lh - 1 : 0;
+    const int r0 = img_ref_start[first + i], r1 = img_ref_start[first + i + 1];
+    const double sigma2x2 = 2.0 * 6.0 * 6.0;
+    double score = 0.0;
+    int max_ref = 0, best_l = 0, best_d = 1 << 30;
+    for (int r = r0; r < r1; ++r) {
+        const int cnt = tb.ref_count[r];
+        double vr = 0.0;
+        for (int e = 0; e < cnt; ++e) {
+            const uint64_t k = tb.ref_keys[(size_t)r * REF_SLOTS + e];
+            if (k == g.key) vr = tb.ref_vec[(size_t)r * REF_SLOTS + e];
+        }
+        const double contrib = g.first ? (g.vec < vr ? g.vec : vr) * vr : 0.0;
+        const double delta = (double)(len_h - tb.ref_len2[r]);
+        const double pen = exp(-(delta * delta) / sigma2x2);
+        double val = seg_sum(contrib);
+        const double nr = tb.ref_norm[(size_t)r * 4 + (lane >> 4)];
+        if (nh != 0.0 && nr != 0.0) val /= (nh * nr);
+        score += val * pen;
+        // BLEU: this lane's n-gram counted in reference r, and the closest reference length
+        const int32_t* rr = ref_tokens + (size_t)r * T;
+        const int Lr = word_len(rr, T);
+        int c = 0;
+        if (g.first)
+            for (int j = 0; j + g.n <= Lr; ++j) c += pack_ngram(rr, g.n, j) == g.key ? 1 : 0;
+        max_ref = c > max_ref ? c : max_ref;
+        const int d = Lr > Lh ? Lr - Lh : Lh - Lr;
+        if (d < best_d || (d == best_d && Lr < best_l)) {
+            best_d = d;
+            best_l = Lr;
+        }
+    }
+    score += __shfl_xor(score, 16);
+    score += __shfl_xor(score, 32);
+    int correct = g.first ? (tf < max_ref ? tf : max_ref) : 0;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) correct += __shfl_xor(correct, o);
+    // ROUGE_L: lane l takes references r0 + l, r0 + l + 64, ...
+    int hw[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) hw[k] = k < Lh ? row[k] : -1;
+    double pmax = 0.0, rmax = 0.0;
+    for (int r = r0 + lane; r < r1; r += 64) {
+        const int32_t* rr = ref_tokens + (size_t)r * T;
+        const int Lr = word_len(rr, T);
+        uint32_t V = ~0u;
+        for (int j = 0; j < Lr; ++j) {
+            const int w = rr[j];
+            uint32_t M = 0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) M |= hw[k] == w ? 1u << k : 0u;
+            const uint32_t U = V & M;
+            V = (V + U) | (V - U);
+        }
+        const int lcs = __popc(~V & ((1u << Lh) - 1u));
+        if (Lh > 0) pmax = fmax(pmax, (double)lcs / (double)Lh);
+        if (Lr > 0) rmax = fmax(rmax, (double)lcs / (double)Lr);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        pmax = fmax(pmax, __shfl_xor(pmax, o));
+        rmax = fmax(rmax, __shfl_xor(rmax, o));
+    }
+    int32_t* st = img_stats + (size_t)i * MET_STATS;
+    if ((lane & 15) == 0) {
+        const int n = (lane >> 4) + 1;
+        st[n - 1] = correct;
+        st[4 + n - 1] = Lh - n + 1 > 0 ? Lh - n + 1 : 0;
+    }
+    if (lane == 0) {
+        st[8] = Lh;
+        st[9] = best_l;
+        const double beta2 = 1.2 * 1.2;
+        img_rouge[i] = (pmax != 0.0 && rmax != 0.0) ? ((1.0 + beta2) * pmax * rmax) / (rmax + beta2 * pmax) : 0.0;
+        double avg = score / 4.0;
+        avg /= (double)(r1 - r0);
+        avg *= 10.0;
+        img_cider[i] = avg;
+    }
+}
+
+// the corpus values, in a fixed order (thread t sums images t, t + 256, ..., thread 0 then the 256 partial sums): the
+// ten BLEU totals as int64, Bleu_1..4 (bleu_scorer.compute_score: tiny = 1e-15, small = 1e-9, the brevity penalty
+// when testlen / reflen < 1), the means of ROUGE_L and CIDEr-D. A faulted decode gives NaN metrics.
+__global__ __launch_bounds__(256) void nicnes_split_metrics_finish_kernel(const int32_t* img_stats, const double* img_rouge,
+                                                                          const double* img_cider, int count,
+                                                                          const int32_t* fault, long long* totals_out,
+                                                                          double* metrics_out) {
+    __shared__ long long st[256][MET_STATS];
+    __shared__ double sr[256], sc[256];
+    const int t = threadIdx.x;
+    long long a[MET_STATS];
+    for (int k = 0; k < MET_STATS; ++k) a[k] = 0;
+    double ar = 0.0, ac = 0.0;
+    for (int i = t; i < count; i += 256) {
+        for (int k = 0; k < MET_STATS; ++k) a[k] += img_stats[(size_t)i * MET_STATS + k];
+        ar += img_rouge[i];
+        ac += img_cider[i];
+    }
+    for (int k = 0; k < MET_STATS; ++k) st[t][k] = a[k];
+    sr[t] = ar;
+    sc[t] = ac;
+    __syncthreads();
+    if (t != 0) return;
+    long long tot[MET_STATS];
+    for (int k = 0; k < MET_STATS; ++k) tot[k] = 0;
+    double rouge = 0.0, cider = 0.0;
+    for (int u = 0; u < 256; ++u) {
+        for (int k = 0; k < MET_STATS; ++k) tot[k] += st[u][k];
+        rouge += sr[u];
+        cider += sc[u];
+    }
+    for (int k = 0; k < MET_STATS; ++k) totals_out[k] = tot[k];
+    if (decode_fault(fault)) {
+        for (int k = 0; k < 6; ++k) metrics_out[k] = __builtin_nan("");
+        return;
+    }
+    const double tiny = 1e-15, small = 1e-9;
+    const double ratio = ((double)tot[8] + tiny) / ((double)tot[9] + small);
+    double bleu = 1.0;
+    for (int k = 0; k < 4; ++k) {
+        bleu *= ((double)tot[k] + tiny) / ((double)tot[4 + k] + small);
+        double b = pow(bleu, 1.0 / (double)(k + 1));
+        if (ratio < 1.0) b *= exp(1.0 - 1.0 / ratio);
+        metrics_out[k] = b;
+    }
+    metrics_out[4] = rouge / (double)count;
+    metrics_out[5] = cider / (double)count;
+}
+
+extern "C" hipError_t nicnes_launch_split_metrics(const int32_t* seq, int first, int count, int T, const CiderTables* tb,
+                                                  const int32_t* img_ref_start, const int32_t* ref_tokens,
+                                                  int32_t* img_stats, double* img_rouge, double* img_cider,
+                                                  int64_t* totals_out, double* metrics_out, hipStream_t stream) {
+    if (count < 1 || T < 1 || T > 16) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nicnes_split_metrics_kernel, dim3((count + 3) / 4), dim3(256), 0, stream, seq, first, count, T, *tb,
+                       img_ref_start, ref_tokens, img_stats, img_rouge, img_cider);
+    hipLaunchKernelGGL(nicnes_split_metrics_finish_kernel, dim3(1), dim3(256), 0, stream, (const int32_t*)img_stats,
+                       (const double*)img_rouge, (const double*)img_cider, count, tb->fault, (long long*)totals_out,
+                       metrics_out);
     return hipGetLastError();
 }

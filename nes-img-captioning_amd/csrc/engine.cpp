@@ -174,6 +174,44 @@ struct nicnes_handle {
     bool step_pending_check = false;
     int64_t t_prev = 0;
     int theta_fp32_prev = 0;
+    std::vector<nicnes_split*> splits;        // resident evaluation splits (nicnes_split_create), freed with the handle
+};
+
+// A resident evaluation split (nicnes_split_create): N images' fc rows, their references cooked WITHOUT the end token
+// against the split's own df table, and the work buffers of its one-call decode. Nothing here is shared with the
+// handle's training batches, df table or evaluate buffers.
+#define SPLIT_ROWS 128          // rows per sign of a pseudo-member: it decodes 2 * SPLIT_ROWS images
+#define SPLIT_MAX_PM 4096       // pseudo-members of one decode (2^20 images, the bound of nicnes_set_batches)
+struct nicnes_split {
+    nicnes_handle* h = nullptr;
+    int32_t N = 0, n_refs = 0;
+    float* fc = nullptr;              // [N + 2 * SPLIT_ROWS, F]: the tail rows (zeros) are decoded and dropped
+    int32_t* ref_tokens = nullptr;    // [n_refs, T]
+    int32_t* img_ref_start = nullptr; // [N + 1]
+    uint64_t* hash_keys = nullptr;    // the split's df table
+    double* hash_vals = nullptr;
+    uint64_t hash_mask = 0;
+    double ref_len = 0.0;
+    uint64_t* ref_keys = nullptr;     // cooked references (CiderTables)
+    double* ref_vec = nullptr;
+    int32_t* ref_count = nullptr;
+    int32_t* ref_len2 = nullptr;
+    double* ref_norm = nullptr;
+    int32_t* img_stats = nullptr;     // per-image BLEU statistics [N, 10], ROUGE_L and CIDEr-D [N]
+    double* img_rouge = nullptr;
+    double* img_cider = nullptr;
+    // decode work, grown to the largest range decoded: pm_cap pseudo-members (tokens, log-probs, lane scratch, alive
+    // flags, coop counters, the zero slice index and the member -> image block map) and wg_cap logit workgroups
+    int32_t pm_cap = 0;
+    int64_t wg_cap = 0;
+    int32_t* seq = nullptr;
+    float* lp = nullptr;
+    float* scratch = nullptr;
+    int32_t* alive = nullptr;
+    uint32_t* coop_ctr = nullptr;
+    uint64_t* zero_idx = nullptr;
+    int32_t* block = nullptr;
+    float* part = nullptr;
 };
 
 namespace {
@@ -469,10 +507,15 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
     return NICNES_OK;
 }
 
+static void split_free(nicnes_split* sp);
+
 int nicnes_destroy(nicnes_handle* h) {
     if (!h) return NICNES_OK;
     (void)hipSetDevice(h->device);
     if (h->comm && h->comm_owned) (void)ncclCommDestroy(h->comm);
+    if (!h->splits.empty()) (void)hipDeviceSynchronize();
+    for (nicnes_split* sp : h->splits) split_free(sp);
+    h->splits.clear();
     void* bufs[] = {h->theta64, h->theta32, h->m, h->v, h->ref_keys, h->ref_vec, h->ref_count, h->ref_len2,
                     h->ref_norm, h->nidx, h->seq, h->lp, h->row_scores, h->dscratch, h->stats, h->partials, h->norms,
                     h->hash_keys, h->hash_vals, h->img_hkey, h->img_hrow, h->img_vr, h->alive, h->part,
@@ -846,6 +889,48 @@ static int score_rollouts(nicnes_handle* h, const int32_t* seq, const float* lp,
     return NICNES_OK;
 }
 
+// The decode of `count` members enqueued on s, or in parts on s and the engine's streams (the one launch sequence of
+// nicnes_evaluate* and nicnes_split_decode). Returns the number of streams used, or -(error code).
+static int launch_decode_parts(nicnes_handle* h, const DecodeParams& p, const MutHead& mh, const ScreenArgs& sa, int count,
+                               int nslabs, hipStream_t s, bool timed, int* n_ev) {
+#define HIPN(expr)                                                                                           \
+    do {                                                                                                     \
+        hipError_t e_ = (expr);                                                                              \
+        if (e_ != hipSuccess) return -fail(h, NICNES_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+    // the coop launch needs all its workgroups resident: never split over streams
+    const int nstr = p.coop ? 1 : std::min(count, h->dec_streams ? h->dec_streams : (p.S == 1 ? 1 : 2));
+    if (nstr > 1) {
+        // members split evenly over the caller's stream and nstr - 1 engine streams; the parts share
+        // nothing but the fallback counter (an atomic). No per-launch events: the launches overlap
+        if (!h->ev_fork) HIPN(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+        for (int i = 0; i < nstr - 1; ++i)
+            if (!h->sx[i]) {
+                HIPN(hipStreamCreateWithFlags(&h->sx[i], hipStreamNonBlocking));
+                HIPN(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
+            }
+        HIPN(hipEventRecord(h->ev_fork, s));
+        for (int i = 0; i < nstr; ++i) {
+            const int a = (int)((int64_t)count * i / nstr), b = (int)((int64_t)count * (i + 1) / nstr);
+            DecodeParams pi = p;
+            MutHead mi = mh;
+            ScreenArgs si_ = sa;
+            nicnes_decode_shift(&pi, a, nslabs, &mi, &si_);
+            hipStream_t si = i == 0 ? s : h->sx[i - 1];
+            if (i > 0) HIPN(hipStreamWaitEvent(si, h->ev_fork, 0));
+            HIPN(nicnes_launch_decode(&pi, &mi, b - a, nslabs, si, nullptr, nullptr, nullptr, &si_));
+        }
+        for (int i = 0; i < nstr - 1; ++i) {
+            HIPN(hipEventRecord(h->ev_join[i], h->sx[i]));
+            HIPN(hipStreamWaitEvent(s, h->ev_join[i], 0));
+        }
+    } else {
+        HIPN(nicnes_launch_decode(&p, &mh, count, nslabs, s, timed ? h->dev : nullptr, h->dev_kind, n_ev, &sa));
+    }
+#undef HIPN
+    return nstr;
+}
+
 // eval_theta: the sigma = 0 rollout of theta itself (count 1), decoded ONCE: sign + takes the first half of the
 // batch's images and sign - the second (at sigma = 0 both signs are theta, so the halves are one decode of the
 // batch), scored as one rollout of B rows
@@ -1069,38 +1154,11 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     if (p.lp) HIPC(h, hipMemsetAsync(p.lp, 0, out_rows * h->cfg.seq_length * sizeof(float), s));
     if (h->timing) HIPC(h, hipEventRecord(h->ev[0], s));
     int n_ev = 0;
-    // the coop launch needs all its workgroups resident: never split over streams
-    const int nstr = p.coop ? 1 : std::min(count, h->dec_streams ? h->dec_streams : (S == 1 ? 1 : 2));
-    if (nstr > 1) {
-        // members split evenly over the caller's stream and nstr - 1 engine streams; the parts share
-        // nothing but the fallback counter (an atomic). No per-launch events: the launches overlap
-        if (!h->ev_fork) HIPC(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        for (int i = 0; i < nstr - 1; ++i)
-            if (!h->sx[i]) {
-                HIPC(h, hipStreamCreateWithFlags(&h->sx[i], hipStreamNonBlocking));
-                HIPC(h, hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
-            }
-        HIPC(h, hipEventRecord(h->ev_fork, s));
-        for (int i = 0; i < nstr; ++i) {
-            const int a = (int)((int64_t)count * i / nstr), b = (int)((int64_t)count * (i + 1) / nstr);
-            DecodeParams pi = p;
-            MutHead mi = mh;
-            ScreenArgs si_ = sa;
-            nicnes_decode_shift(&pi, a, nslabs, &mi, &si_);
-            hipStream_t si = i == 0 ? s : h->sx[i - 1];
-            if (i > 0) HIPC(h, hipStreamWaitEvent(si, h->ev_fork, 0));
-            HIPC(h, nicnes_launch_decode(&pi, &mi, b - a, nslabs, si, nullptr, nullptr, nullptr, &si_));
-        }
-        for (int i = 0; i < nstr - 1; ++i) {
-            HIPC(h, hipEventRecord(h->ev_join[i], h->sx[i]));
-            HIPC(h, hipStreamWaitEvent(s, h->ev_join[i], 0));
-        }
-    } else {
-        HIPC(h, nicnes_launch_decode(&p, &mh, count, nslabs, s, h->timing ? h->dev : nullptr, h->dev_kind, &n_ev, &sa));
-    }
+    const int nstr = launch_decode_parts(h, p, mh, sa, count, nslabs, s, h->timing, &n_ev);
+    if (nstr < 0) return -nstr;
     h->n_dev = h->timing ? n_ev : 0;
     h->multi_stream = nstr > 1;
-    if (p.no_exit)      // eval_theta: the two halves are one rollout
+    if (p.no_exit)    // eval_theta: the two halves are one rollout
         HIPC(h, nicnes_launch_lp_batch_exit(p.seq, p.lp, eval_theta ? 1 : 2 * count, rows_total, h->cfg.seq_length, s));
     if (h->timing) HIPC(h, hipEventRecord(h->ev[1], s));
     if (!h->stats_pending) {          // read the fallback counter back without a host wait
@@ -1130,6 +1188,309 @@ int nicnes_evaluate_theta(nicnes_handle* h, int32_t batch, uint64_t iteration, d
     const int32_t mb = batch;
     return evaluate_impl(h, iteration, 0, 1, 0.f, h->n_batches > 1 ? &mb : nullptr, fitness_out, seq_out, logprob_out,
                          stream, true);
+}
+
+// ---- resident evaluation splits ---------------------------------------------------------------------------------
+static void split_free(nicnes_split* sp) {
+    void* bufs[] = {sp->fc, sp->ref_tokens, sp->img_ref_start, sp->hash_keys, sp->hash_vals, sp->ref_keys, sp->ref_vec,
+                    sp->ref_count, sp->ref_len2, sp->ref_norm, sp->img_stats, sp->img_rouge, sp->img_cider, sp->seq, sp->lp,
+                    sp->scratch, sp->alive, sp->coop_ctr, sp->zero_idx, sp->block, sp->part};
+    for (void* q : bufs)
+        if (q) (void)hipFree(q);
+    delete sp;
+}
+
+static CiderTables split_tables(const nicnes_handle* h, const nicnes_split* sp) {
+    CiderTables tb{};
+    tb.hash_keys = sp->hash_keys;
+    tb.hash_vals = sp->hash_vals;
+    tb.hash_mask = sp->hash_mask;
+    tb.ref_len = sp->ref_len;
+    tb.ref_keys = sp->ref_keys;
+    tb.ref_vec = sp->ref_vec;
+    tb.ref_count = sp->ref_count;
+    tb.ref_len2 = sp->ref_len2;
+    tb.ref_norm = sp->ref_norm;
+    tb.fault = h->stats;
+    return tb;
+}
+
+static bool split_of(const nicnes_handle* h, const nicnes_split* sp) {
+    return h && sp && std::find(h->splits.begin(), h->splits.end(), sp) != h->splits.end();
+}
+
+int nicnes_split_create(nicnes_handle* h, const float* fc, int32_t N, const int32_t* ref_tokens, int32_t n_refs,
+                        const int32_t* img_ref_start, const uint64_t* df_keys, const double* df, int64_t n_df,
+                        double ref_len_log, nicnes_split** out, void* stream) {
+    if (!h || !fc || !out) return NICNES_ERR_INVALID;
+    *out = nullptr;
+    if (N < 1 || N > (1 << 20)) return fail(h, NICNES_ERR_INVALID, "N out of [1, 2^20]");
+    if (n_refs < 0 || n_df < 0) return fail(h, NICNES_ERR_INVALID, "negative count");
+    if (n_refs > 0 && (!ref_tokens || !img_ref_start)) return fail(h, NICNES_ERR_INVALID, "references without their arrays");
+    if (n_refs > 0 && n_refs < N) return fail(h, NICNES_ERR_INVALID, "n_refs < images");
+    if (n_refs > 0 && n_df > 0 && (!df_keys || !df)) return fail(h, NICNES_ERR_INVALID, "df table without its arrays");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipStreamSynchronize(s));        // the caller's arrays may have been written on its stream
+    const size_t F = (size_t)h->cfg.fc_feat_size, T = (size_t)h->cfg.seq_length;
+    std::vector<int32_t> st;
+    if (n_refs > 0) {                        // reference ranges as nicnes_set_batches checks them
+        st.resize((size_t)N + 1);
+        HIPC(h, hipMemcpy(st.data(), img_ref_start, st.size() * sizeof(int32_t), hipMemcpyDefault));
+        bool ok = st[0] == 0 && st[N] == n_refs;
+        for (int b = 0; b < N && ok; ++b) ok = st[b + 1] > st[b];
+        if (!ok)
+            return fail(h, NICNES_ERR_INVALID,
+                        "img_ref_start must start at 0, end at n_refs and give every image >= 1 reference");
+    }
+    nicnes_split* sp = new nicnes_split();
+    sp->h = h;
+    sp->N = N;
+    sp->n_refs = n_refs;
+    sp->ref_len = ref_len_log;
+    uint64_t* tk = nullptr;                  // the caller's df table on the device, while the hash copy is built
+    double* tv = nullptr;
+    auto run = [&]() -> int {
+        const size_t pad = 2 * SPLIT_ROWS;
+        int rc = dalloc(h, &sp->fc, ((size_t)N + pad) * F);
+        if (rc) return rc;
+        HIPC(h, hipMemcpy(sp->fc, fc, (size_t)N * F * sizeof(float), hipMemcpyDefault));
+        HIPC(h, hipMemset(sp->fc + (size_t)N * F, 0, pad * F * sizeof(float)));
+        if (n_refs == 0) return NICNES_OK;  // a decode-only split
+        const size_t NR = (size_t)n_refs;
+        rc = dalloc(h, &sp->ref_tokens, NR * T);
+        if (!rc) rc = dalloc(h, &sp->img_ref_start, (size_t)N + 1);
+        if (!rc) rc = dalloc(h, &sp->ref_keys, NR * 64);
+        if (!rc) rc = dalloc(h, &sp->ref_vec, NR * 64);
+        if (!rc) rc = dalloc(h, &sp->ref_count, NR);
+        if (!rc) rc = dalloc(h, &sp->ref_len2, NR);
+        if (!rc) rc = dalloc(h, &sp->ref_norm, NR * 4);
+        if (!rc) rc = dalloc(h, &sp->img_stats, (size_t)N * 10);
+        if (!rc) rc = dalloc(h, &sp->img_rouge, (size_t)N);
+        if (!rc) rc = dalloc(h, &sp->img_cider, (size_t)N);
+        const uint64_t cap = nicnes_df_hash_capacity(n_df);
+        if (!rc) rc = dalloc(h, &sp->hash_keys, cap);
+        if (!rc) rc = dalloc(h, &sp->hash_vals, cap);
+        if (rc) return rc;
+        HIPC(h, hipMemcpy(sp->ref_tokens, ref_tokens, NR * T * sizeof(int32_t), hipMemcpyDefault));
+        HIPC(h, hipMemcpy(sp->img_ref_start, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPC(h, hipMemset(sp->hash_keys, 0, cap * sizeof(uint64_t)));
+        sp->hash_mask = cap - 1;
+        if (n_df > 0) {
+            rc = dalloc(h, &tk, (size_t)n_df);
+            if (!rc) rc = dalloc(h, &tv, (size_t)n_df);
+            if (rc) return rc;
+            HIPC(h, hipMemcpy(tk, df_keys, (size_t)n_df * sizeof(uint64_t), hipMemcpyDefault));
+            HIPC(h, hipMemcpy(tv, df, (size_t)n_df * sizeof(double), hipMemcpyDefault));
+            HIPC(h, nicnes_launch_df_hash_build(tk, tv, n_df, sp->hash_keys, sp->hash_vals, sp->hash_mask, s));
+        }
+        const CiderTables tb = split_tables(h, sp);
+        HIPC(h, nicnes_launch_cook_refs(sp->ref_tokens, n_refs, (int)T, &tb, s, 1));
+        HIPC(h, hipStreamSynchronize(s));
+        return NICNES_OK;
+    };
+    const int rc = run();
+    if (tk) (void)hipFree(tk);
+    if (tv) (void)hipFree(tv);
+    if (rc) {
+        split_free(sp);
+        return rc;
+    }
+    h->splits.push_back(sp);
+    *out = sp;
+    return NICNES_OK;
+}
+
+int nicnes_split_destroy(nicnes_handle* h, nicnes_split* sp) {
+    if (!h) return NICNES_ERR_INVALID;
+    if (!sp) return NICNES_OK;
+    if (!split_of(h, sp)) return fail(h, NICNES_ERR_INVALID, "not a split of this handle");
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipDeviceSynchronize());
+    h->splits.erase(std::find(h->splits.begin(), h->splits.end(), sp));
+    split_free(sp);
+    return NICNES_OK;
+}
+
+// the decode work buffers for n_pm pseudo-members and n_lwg logit workgroups (grown outside every launch)
+static int split_grow(nicnes_handle* h, nicnes_split* sp, int n_pm, int64_t n_lwg) {
+    const size_t T = (size_t)h->cfg.seq_length;
+    if (n_pm > sp->pm_cap) {
+        HIPC(h, hipDeviceSynchronize());
+        void* old[] = {sp->seq, sp->lp, sp->scratch, sp->alive, sp->coop_ctr, sp->zero_idx, sp->block};
+        for (void* q : old)
+            if (q) (void)hipFree(q);
+        sp->seq = nullptr; sp->lp = nullptr; sp->scratch = nullptr; sp->alive = nullptr; sp->coop_ctr = nullptr;
+        sp->zero_idx = nullptr; sp->block = nullptr;
+        sp->pm_cap = 0;
+        const size_t PM = (size_t)n_pm, rows = PM * 2 * SPLIT_ROWS;
+        // a pseudo-member is one 128-row slab or two 64-row slabs: 8 row waves of lane scratch, <= 2 workgroups
+        int rc = dalloc(h, &sp->seq, rows * T);
+        if (!rc) rc = dalloc(h, &sp->lp, rows * T);
+        if (!rc) rc = dalloc(h, &sp->scratch, nicnes_decode_scratch_floats(n_pm, 8));
+        if (!rc) rc = dalloc(h, &sp->alive, 3 * 2 * PM);
+        if (!rc) rc = dalloc(h, &sp->coop_ctr, 2 * PM * COOP_CTR_STRIDE);
+        if (!rc) rc = dalloc(h, &sp->zero_idx, PM);
+        if (!rc) rc = dalloc(h, &sp->block, PM);
+        if (rc) return rc;
+        std::vector<int32_t> iota(PM);
+        for (size_t k = 0; k < PM; ++k) iota[k] = (int32_t)k;
+        HIPC(h, hipMemcpy(sp->block, iota.data(), PM * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPC(h, hipMemset(sp->zero_idx, 0, PM * sizeof(uint64_t)));
+        sp->pm_cap = n_pm;
+    }
+    if (n_lwg > sp->wg_cap) {
+        HIPC(h, hipDeviceSynchronize());
+        if (sp->part) (void)hipFree(sp->part);
+        sp->part = nullptr;
+        sp->wg_cap = 0;
+        int rc = dalloc(h, &sp->part, (size_t)n_lwg * PART_FLOATS);
+        if (rc) return rc;
+        sp->wg_cap = n_lwg;
+    }
+    return NICNES_OK;
+}
+
+// log-probs of the steps after a row's end token are 0 (a decode leaves what its workgroup's other rows still ran)
+__global__ void split_lp_mask_kernel(const int32_t* seq, float* lp, int rows, int T) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= rows) return;
+    bool ended = false;
+    for (int t = 0; t < T; ++t) {
+        if (ended) lp[(size_t)b * T + t] = 0.f;
+        if (seq[(size_t)b * T + t] == 0) ended = true;
+    }
+}
+
+// The greedy decode of theta on images [first, first + count), every slab in one enqueue: nicnes_evaluate_theta's
+// halves (sign_off, the zero noise slice, member_batch) over ceil(count / 256) pseudo-members, pseudo-member k
+// decoding images first + 256 k + (0..127) as its sign + and the next 128 as its sign -. Rows past the range are
+// decoded (other images of the split, or the zero rows behind it) and dropped. *seq_dev: the tokens in the split's
+// own buffer [count, T]; seq_out / lp_out (nullable) receive copies.
+static int split_decode_impl(nicnes_handle* h, nicnes_split* sp, int32_t first, int32_t count, int32_t* seq_out,
+                             float* lp_out, hipStream_t s, const int32_t** seq_dev) {
+    if (!split_of(h, sp)) return fail(h, NICNES_ERR_INVALID, "not a split of this handle");
+    if (first < 0 || count < 1 || (int64_t)first + count > sp->N)
+        return fail(h, NICNES_ERR_INVALID, "range outside the split's images");
+    if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
+    HIPC(h, hipSetDevice(h->device));
+    const int per = 2 * SPLIT_ROWS, n_pm = (count + per - 1) / per;
+    if (n_pm > SPLIT_MAX_PM) return fail(h, NICNES_ERR_INVALID, "range beyond the decode buffers");
+    int G = 0, nslabs = 0, S = 0;
+    decode_shape(h, SPLIT_ROWS, n_pm, &G, &nslabs, &S);
+    if (int rc = ensure_zero_noise(h)) return rc;
+    if (int rc = split_grow(h, sp, n_pm, (int64_t)n_pm * nslabs * S)) return rc;
+    const int T = h->cfg.seq_length;
+    DecodeParams p;
+    p.theta = h->theta32;
+    p.noise = h->zero_noise;
+    p.noise_idx = sp->zero_idx;
+    p.fc = sp->fc + (size_t)first * h->cfg.fc_feat_size;
+    p.member_batch = sp->block;
+    p.seq = sp->seq;
+    p.lp = lp_out ? sp->lp : nullptr;
+    p.sample_u = nullptr;
+    p.slog = nullptr;
+    p.slog_slots = nullptr;
+    p.slog_ns = 0;
+    p.scratch = sp->scratch;
+    p.stats = h->stats;
+    p.alive = sp->alive;
+    p.alive_stride = 2 * sp->pm_cap;
+    p.alive2 = sp->alive + p.alive_stride;
+    p.part = sp->part;
+    p.coop_ctr = sp->coop_ctr;
+    p.force_exact = h->force_exact;
+    p.lse_margin = h->lse_margin;
+    // the lse mode of the engine's policy as it stands (tokens do not depend on it); the policy's own state and the
+    // counter read-back belong to the evaluates
+    const bool bounded = h->bounded_mode == 1 || (h->bounded_mode == 2 && h->exact_left == 0);
+    p.bounded_lse = bounded ? 1 : 0;
+    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr};
+    const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)n_pm * nslabs > h->n_cu);
+    if (screen_on && !p.lp && bounded && G == 4 && S == 1 && h->screen_cap && h->screen_norm &&
+        (int64_t)n_pm * nslabs <= h->screen_wgs && n_pm <= h->cfg.max_members) {
+        sa.cap = h->screen_cap;
+        sa.norm = h->screen_norm;
+    }
+    p.G = G;
+    p.S = S;
+    p.coop = coop_fits(h, G, nslabs, S, n_pm) ? 1 : 0;
+    p.coop_launch = h->coop_launch;
+    p.test_stall_ms = 0;
+    p.no_exit = 0;      // a row's log-probs up to its own end token are written before its workgroup exits
+    p.no_mask = 0;
+    p.B = SPLIT_ROWS;
+    p.B_img = per;
+    p.rpi = 1;
+    p.sign_off = SPLIT_ROWS;
+    p.F = h->cfg.fc_feat_size;
+    p.V1 = h->V1;
+    p.T = T;
+    p.D = h->D;
+    p.off_img_w = h->off[0];
+    p.off_img_b = h->off[1];
+    p.off_emb_w = h->off[2];
+    p.off_log_w = h->off[3];
+    p.off_log_b = h->off[4];
+    p.off_i2h_w = h->off[5];
+    p.off_i2h_b = h->off[6];
+    p.off_h2h_w = h->off[7];
+    p.off_h2h_b = h->off[8];
+    const size_t out_rows = (size_t)n_pm * per;
+    HIPC(h, hipMemsetAsync(p.seq, 0, out_rows * T * sizeof(int32_t), s));
+    if (p.lp) HIPC(h, hipMemsetAsync(p.lp, 0, out_rows * T * sizeof(float), s));
+    const MutHead mh{nullptr, nullptr, nullptr, 0};
+    const int nstr = launch_decode_parts(h, p, mh, sa, n_pm, nslabs, s, false, nullptr);
+    if (nstr < 0) return -nstr;
+    if (p.lp) {
+        hipLaunchKernelGGL(split_lp_mask_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s,
+                           (const int32_t*)p.seq, p.lp, count, T);
+        HIPC(h, hipGetLastError());
+        HIPC(h, hipMemcpyAsync(lp_out, p.lp, (size_t)count * T * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    if (seq_out) HIPC(h, hipMemcpyAsync(seq_out, p.seq, (size_t)count * T * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (seq_dev) *seq_dev = p.seq;
+    return NICNES_OK;
+}
+
+int nicnes_split_decode(nicnes_handle* h, nicnes_split* sp, int32_t first, int32_t count, int32_t* seq_out,
+                        float* lp_out, void* stream) {
+    if (!h || !sp || !seq_out) return NICNES_ERR_INVALID;
+    return split_decode_impl(h, sp, first, count, seq_out, lp_out, (hipStream_t)stream, nullptr);
+}
+
+static int split_score_impl(nicnes_handle* h, nicnes_split* sp, int32_t first, int32_t count, const int32_t* seq,
+                            int64_t* totals_out, double* metrics_out, double* row_cider_out, hipStream_t s) {
+    if (!split_of(h, sp)) return fail(h, NICNES_ERR_INVALID, "not a split of this handle");
+    if (sp->n_refs == 0) return fail(h, NICNES_ERR_INVALID, "a decode-only split has no references to score against");
+    if (first < 0 || count < 1 || (int64_t)first + count > sp->N)
+        return fail(h, NICNES_ERR_INVALID, "range outside the split's images");
+    HIPC(h, hipSetDevice(h->device));
+    const CiderTables tb = split_tables(h, sp);
+    HIPC(h, nicnes_launch_split_metrics(seq, first, count, h->cfg.seq_length, &tb, sp->img_ref_start, sp->ref_tokens,
+                                        sp->img_stats, sp->img_rouge, sp->img_cider, totals_out, metrics_out, s));
+    if (row_cider_out)
+        HIPC(h, hipMemcpyAsync(row_cider_out, sp->img_cider, (size_t)count * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return NICNES_OK;
+}
+
+int nicnes_split_score(nicnes_handle* h, nicnes_split* sp, int32_t first, int32_t count, const int32_t* seq_dev,
+                       int64_t* totals_out_dev, double* metrics_out_dev, double* row_cider_out_dev, void* stream) {
+    if (!h || !sp || !seq_dev || !totals_out_dev || !metrics_out_dev) return NICNES_ERR_INVALID;
+    return split_score_impl(h, sp, first, count, seq_dev, totals_out_dev, metrics_out_dev, row_cider_out_dev,
+                            (hipStream_t)stream);
+}
+
+int nicnes_split_evaluate(nicnes_handle* h, nicnes_split* sp, int32_t first, int32_t count, int64_t* totals_out_dev,
+                          double* metrics_out_dev, double* row_cider_out_dev, int32_t* seq_out, void* stream) {
+    if (!h || !sp || !totals_out_dev || !metrics_out_dev) return NICNES_ERR_INVALID;
+    if (split_of(h, sp) && sp->n_refs == 0)
+        return fail(h, NICNES_ERR_INVALID, "a decode-only split has no references to score against");
+    const int32_t* seq = nullptr;
+    if (int rc = split_decode_impl(h, sp, first, count, seq_out, nullptr, (hipStream_t)stream, &seq)) return rc;
+    return split_score_impl(h, sp, first, count, seq, totals_out_dev, metrics_out_dev, row_cider_out_dev,
+                            (hipStream_t)stream);
 }
 
 int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, float* out, void* stream) {

@@ -170,6 +170,15 @@ class Engine:
         self.B = B
         self.n_batches = len(fcs)
 
+    def make_split(self, fc, gts=None, df=None, ref_len_raw=None):
+        """A resident evaluation split (nicnes_split_create): fc [N, F] fp32, gts per image an int array
+        [n_i, seq_length] of zero-padded label rows (None: a decode-only split). df: the split's own document
+        frequencies, {n-gram tuple: count} or (sorted uint64 keys, counts); None builds the corpus df from gts (every
+        distinct n-gram over an image's references counts once, ref_len_raw = the number of images: what
+        COCOEvalCap's Cider does). The training batches, the handle's df table and every setter's state stay as
+        they are."""
+        return Split(self, fc, gts, df, ref_len_raw)
+
     # ---------------------------------------------------------------- the hot path -------
     def noise_indices(self, iteration, member_begin, count):
         out = torch.empty(count, dtype=torch.int64, device=self.device)
@@ -522,3 +531,129 @@ class Engine:
         check(self.L.nicnes_screen_stats(self.h, sc), self.h, 'screen_stats')
         return {'tie_fallbacks': out[0], 'sample_stage_fallbacks': out[1], 'coop_timeouts': out[2],
                 'sample_slot_timeouts': out[3], 'screen_candidates': sc[0], 'screen_fallback_rows': sc[1]}
+
+
+METRIC_KEYS = ('Bleu_1', 'Bleu_2', 'Bleu_3', 'Bleu_4', 'ROUGE_L', 'CIDEr')   # COCOEvalCap's keys (no java scorers)
+
+
+class Split:
+    """N images held on the GPU for validation: one-call greedy decode of theta and COCOEvalCap's BLEU / ROUGE_L /
+    CIDEr on the label rows (nicnes_split_*; Engine.make_split)."""
+
+    def __init__(self, engine, fc, gts=None, df=None, ref_len_raw=None):
+        from .validation import corpus_df
+        e = self.engine = engine
+        T = e.cfg.seq_length
+        fc_np = fc.detach().cpu().numpy() if isinstance(fc, torch.Tensor) else np.asarray(fc)
+        fc_np = np.ascontiguousarray(fc_np, np.float32)
+        if fc_np.ndim != 2 or fc_np.shape[1] != e.cfg.fc_feat_size or fc_np.shape[0] < 1:
+            raise ValueError('fc must be [N >= 1, fc_feat_size]')
+        self.N = int(fc_np.shape[0])
+        self.has_refs = gts is not None
+        refs_np = np.zeros((0, T), np.int32)
+        start = np.zeros(self.N + 1, np.int32)
+        keys = np.zeros(0, np.uint64)
+        vals = np.zeros(0, np.float64)
+        ref_len_log = 0.0
+        if self.has_refs:
+            if len(gts) != self.N:
+                raise ValueError('gts has %d images, fc has %d rows' % (len(gts), self.N))
+            rows = [np.asarray(g, np.int32).reshape(-1, T) for g in gts]
+            start = np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(np.int32)
+            refs_np = np.ascontiguousarray(np.concatenate(rows, 0))
+            # as set_batches: an id outside the vocabulary would alias another word in the 14-bit key fields
+            if refs_np.size and (refs_np.min() < 0 or refs_np.max() > e.cfg.vocab_size):
+                raise ValueError('reference token outside [0, vocab_size = %d]: min %d, max %d'
+                                 % (e.cfg.vocab_size, refs_np.min(), refs_np.max()))
+            if df is None:
+                keys, vals = corpus_df(rows, T)
+                ref_len_raw = self.N if ref_len_raw is None else ref_len_raw
+            elif isinstance(df, dict):
+                keys, vals = df_table_arrays(df)
+            else:
+                keys, vals = np.asarray(df[0], np.uint64), np.asarray(df[1], np.float64)
+            if ref_len_raw is None:
+                raise ValueError('a given df table needs its ref_len_raw')
+            ref_len_log = float(np.log(float(ref_len_raw)))
+        keys = np.ascontiguousarray(keys, np.uint64)
+        vals = np.ascontiguousarray(vals, np.float64)
+        sp = ctypes.c_void_p()
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)     # noqa: E731  (host arrays: the call copies them)
+        with torch.cuda.device(e.device):
+            check(e.L.nicnes_split_create(e.h, vp(fc_np), self.N, vp(refs_np), int(refs_np.shape[0]), vp(start),
+                                          vp(keys), vp(vals), int(keys.size), ref_len_log, ctypes.byref(sp),
+                                          e._stream()), e.h, 'split_create')
+        self.sp = sp
+
+    def close(self):
+        if getattr(self, 'sp', None) and getattr(self.engine, 'h', None):
+            self.engine.L.nicnes_split_destroy(self.engine.h, self.sp)
+        self.sp = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _range(self, first, count):
+        first = int(first)
+        count = self.N - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.N:
+            raise ValueError('range [%d, %d) outside the split\'s %d images' % (first, first + count, self.N))
+        return first, count
+
+    def decode(self, first=0, count=None, return_lp=False):
+        """Greedy tokens [count, T] int32 of the engine's current theta on images [first, first + count), in one
+        enqueue; return_lp adds each token's log-prob (0 after a row's end token)."""
+        e = self.engine
+        first, count = self._range(first, count)
+        seq = torch.empty((count, e.cfg.seq_length), dtype=torch.int32, device=e.device)
+        lp = torch.empty((count, e.cfg.seq_length), dtype=torch.float32, device=e.device) if return_lp else None
+        with torch.cuda.device(e.device):
+            check(e.L.nicnes_split_decode(e.h, self.sp, first, count, _ptr(seq), _ptr(lp), e._stream()), e.h,
+                  'split_decode')
+        return (seq, lp) if return_lp else seq
+
+    def _outputs(self, count, rows):
+        e = self.engine
+        return (torch.empty(10, dtype=torch.int64, device=e.device), torch.empty(6, dtype=torch.float64, device=e.device),
+                torch.empty(count, dtype=torch.float64, device=e.device) if rows else None)
+
+    @staticmethod
+    def _result(totals, metrics, rows, detail):
+        m = metrics.cpu().numpy()
+        out = {k: float(v) for k, v in zip(METRIC_KEYS, m)}
+        if not detail:
+            return out
+        return out, totals.cpu().numpy(), (rows.cpu().numpy() if rows is not None else None)
+
+    def score(self, seq, first=0, detail=False):
+        """The metrics of GIVEN token rows seq [count, T] as the captions of images [first, first + count):
+        {'Bleu_1'..'Bleu_4', 'ROUGE_L', 'CIDEr'}; detail=True adds the ten BLEU totals (int64: correct[1..4],
+        guess[1..4], testlen, reflen) and every image's CIDEr-D."""
+        e = self.engine
+        sq = e._dev(seq, torch.int32)
+        if sq.dim() != 2 or sq.shape[1] != e.cfg.seq_length:
+            raise ValueError('seq must be [count, seq_length]')
+        if sq.numel() and (int(sq.min()) < 0 or int(sq.max()) > e.cfg.vocab_size):
+            raise ValueError('token outside [0, vocab_size = %d]' % e.cfg.vocab_size)
+        first, count = self._range(first, int(sq.shape[0]))
+        totals, metrics, rows = self._outputs(count, detail)
+        with torch.cuda.device(e.device):
+            check(e.L.nicnes_split_score(e.h, self.sp, first, count, _ptr(sq), _ptr(totals), _ptr(metrics), _ptr(rows),
+                                         e._stream()), e.h, 'split_score')
+            torch.cuda.current_stream().synchronize()    # sq stays alive until the kernels have read it
+        return self._result(totals, metrics, rows, detail)
+
+    def evaluate(self, first=0, count=None, detail=False, return_seq=False):
+        """decode + score in one call: COCOEvalCap's dict for the engine's current theta on the split."""
+        e = self.engine
+        first, count = self._range(first, count)
+        totals, metrics, rows = self._outputs(count, detail)
+        seq = torch.empty((count, e.cfg.seq_length), dtype=torch.int32, device=e.device) if return_seq else None
+        with torch.cuda.device(e.device):
+            check(e.L.nicnes_split_evaluate(e.h, self.sp, first, count, _ptr(totals), _ptr(metrics), _ptr(rows),
+                                            _ptr(seq), e._stream()), e.h, 'split_evaluate')
+        res = self._result(totals, metrics, rows, detail)
+        return (res, seq) if return_seq else res

@@ -10,7 +10,11 @@
                        chunks of the current task and pushes one NESResult per member
   save_snapshot        theta .pth + optimizer.tar + z_info json (/root/reference/src/algorithm/tools/snapshot.py:14-38,
                        optimizers.py:85-107)
-Validation-set evaluation, elites/podium and plotting are outside the engine's scope.
+  EngineMaster(validator=...)
+                       the validation score of every iteration's theta (NESWorker.accuracy -> CaptPolicy.accuracy_on,
+                       nicnes.validation.Validator), the best theta (Podium with num_elites = 1,
+                       src/algorithm/tools/podium.py) and the patience rule (iteration.py:117-148)
+Plotting, and a podium of more than one elite, are outside the engine's scope.
 """
 import json
 import os
@@ -42,10 +46,12 @@ class Schedule:
         self.patience = config.patience
         self.nb_offspring = int(nb_offspring)
         self.schedule_reached = False
+        self.patience_reached = False
 
     def incr_iteration(self):
         """iteration.py:165-182"""
         self.schedule_reached = False
+        self.patience_reached = False
         self.iteration += 1
         self.nb_samples_used += self.batch_size
         if self.check_schedule_limit():
@@ -62,6 +68,21 @@ class Schedule:
         self.batch_size = int(self.batch_size * self.bs_multiplier)
         self.times_orig_bs *= self.bs_multiplier
 
+    def record_generation(self, bad):
+        """iteration.py:135-147 (process_evaluated_elites): a generation without a new best elite counts against the
+        patience; beyond it the curriculum moves a step and the count restarts. patience = 0 (or None) disables it.
+        Returns True when the step was taken."""
+        if self.patience and bad:
+            self.bad_generations += 1
+            if self.bad_generations > self.patience:
+                self.next_curriculum_step()
+                self.patience_reached = True
+                self.bad_generations = 0
+                return True
+        else:
+            self.bad_generations = 0
+        return False
+
     def to_dict(self):
         return {'iter': self.iteration, 'epoch': self.epoch, 'noise_stdev': self.noise_stdev,
                 'batch_size': self.batch_size, 'bad_generations': self.bad_generations,
@@ -77,7 +98,8 @@ class Schedule:
 
 
 class EngineMaster:
-    def __init__(self, spec, engine, log_dir=None, rank=0, world_size=1, group=None, theta=None, comm=None):
+    def __init__(self, spec, engine, log_dir=None, rank=0, world_size=1, group=None, theta=None, comm=None,
+                 validator=None):
         self.spec, self.e = spec, engine
         self.log_dir = log_dir or spec.config.log_dir or 'logs/nicnes'
         self.rank, self.world, self.group, self.comm = rank, world_size, group, comm
@@ -88,6 +110,14 @@ class EngineMaster:
         self.opt = make_optimizer(engine, spec)
         self.stats = []
         self.faults = []
+        # validation (None: no score, no podium, no patience -- the loop is unchanged). With several ranks rank 0
+        # validates and the score is shared in a collective, so EVERY rank passes validator (only rank 0's is used:
+        # the other ranks may pass True instead of holding the split too)
+        self.validator = validator
+        self.validate = validator is not None
+        self.val_score = None
+        self.best_val_score = float('-inf')
+        self.best_elites = []                   # [(path, score)]: Podium with num_elites = 1
         self._batch_key = None
         self._n_batches = 1
         self.mutator = None
@@ -125,11 +155,49 @@ class EngineMaster:
     def _update(self, gsum, P):
         return self.opt.update_from_noise_sum(gsum, P, self.spec.l2coeff)
 
+    def best_model_path(self):
+        """models/best/best_elite/0_0_elite.pth (Podium's directory and file name for elite 0 of offspring 0)"""
+        d = os.path.join(self.log_dir, 'models', 'best', 'best_elite')
+        os.makedirs(d, exist_ok=True)
+        return os.path.join(d, '0_0_elite.pth')
+
+    def _validate(self):
+        """The validation score of the theta this iteration evaluates (the pre-update theta, as the reference's eval
+        run of the current task scores it): rank 0 validates, every rank gets the score, so every rank's schedule
+        moves alike. A new best theta is written to best_model_path() (rank 0). Returns True for a bad generation
+        (no new best), None without validation."""
+        if not self.validate:
+            return None
+        score = self.policy.accuracy_on(self.validator) if self.rank == 0 else 0.0
+        if self.world > 1:
+            t = torch.zeros((1, 2), dtype=torch.float64, device=self.e.device)
+            t[0, 0] = score
+            if self.comm == 'engine':
+                allv = torch.empty((self.world, 2), dtype=torch.float64, device=self.e.device)
+                self.e.allgather_fitness(t, allv)
+                score = float(allv[0, 0].item())
+            else:
+                import torch.distributed as dist
+                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)      # the other ranks add 0
+                score = float(t[0, 0].item())
+        self.val_score = score
+        bad = not score > self.best_val_score
+        if not bad:
+            self.best_val_score = score
+            path = self.best_model_path()
+            if self.rank == 0:
+                t64, t32 = self.e.theta()
+                torch.save(state_dict_from_vector(t32 if self.opt.t == 0 else t64, param_shapes(self.e)), path)
+            self.best_elites = [(path, score)]
+        return bad
+
     def _record(self, fit, ratio, t0):
         f = fit.detach().cpu().numpy() if isinstance(fit, torch.Tensor) else np.asarray(fit)
         rec = {'iter': self.sched.iteration, 'update_ratio': float(ratio), 'score_mean': float(f.mean()),
                'score_max': float(f.max()), 'score_min': float(f.min()), 'noise_stdev': self.sched.noise_stdev,
                'batch_size': self.sched.batch_size, 'step_time': time.time() - t0}
+        if self.validate:
+            rec['val_score'], rec['best_val_score'] = self.val_score, self.best_val_score
         self.stats.append(rec)
         return rec
 
@@ -141,7 +209,7 @@ class EngineMaster:
     def _after_update(self):
         """nic_nes_master.py:139-141,161-163: when the schedule is reached the Adam step size is
         divided by stepsize_divisor (the noise / batch curriculum already moved in incr_iteration)."""
-        if self.sched.schedule_reached and self.spec.config.stepsize_divisor:
+        if (self.sched.schedule_reached or self.sched.patience_reached) and self.spec.config.stepsize_divisor:
             self.opt.stepsize /= self.spec.config.stepsize_divisor
 
     def _batch_stream(self, batches):
@@ -217,6 +285,7 @@ class EngineMaster:
                 if runner is None or runner.sigma != self.sched.noise_stdev:
                     runner = PopulationRunner(self.e, P, self.sched.noise_stdev, rank=self.rank,
                                               world_size=self.world, group=self.group, comm=self.comm)
+                bad_gen = self._validate()
                 for attempt in range(int(fault_retries) + 1):
                     try:
                         fit, ratio = self._iterate(runner, P)
@@ -231,12 +300,14 @@ class EngineMaster:
                             if self.rank == 0:
                                 self.save_snapshot()
                             raise
+                if bad_gen is not None:
+                    self.sched.record_generation(bad_gen)
                 self._record(fit, ratio, t0)
                 self._after_update()
                 self._maybe_snapshot()
                 if max_it and self.sched.iteration >= max_it:
                     return self.stats
-                if self.sched.schedule_reached and not hasattr(batches, 'get_batch'):
+                if (self.sched.schedule_reached or self.sched.patience_reached) and not hasattr(batches, 'get_batch'):
                     break          # batch size changed: the caller's iterable yields new batches
             if not yielded:
                 return self.stats  # an exhausted one-shot iterator: nothing more to evaluate
@@ -271,6 +342,7 @@ class EngineMaster:
             self._set_batch(batch)
             self._prepare_mutation(batch)
             sigma = self.sched.noise_stdev
+            bad_gen = self._validate()
             task_id = client.declare_task(NESTask(current=self.serialize_current(), batch_data=batch,
                                                   noise_stdev=sigma, batch_size=self.sched.batch_size,
                                                   iteration=self.sched.iteration))
@@ -290,6 +362,8 @@ class EngineMaster:
             _, w = self.e.rank_weights(fit_t)
             gsum = self.e.grad_partial(self.sched.iteration, 0, P, w, sigma)
             ratio = self._update(gsum, P)
+            if bad_gen is not None:
+                self.sched.record_generation(bad_gen)
             self._record(fit, ratio, t0)
             self._after_update()
             self._maybe_snapshot()
@@ -307,6 +381,8 @@ class EngineMaster:
                 os.remove(os.path.join(d, f))
         infos = {**self.sched.to_dict(), 'current_model': theta_path,
                  'optimizer_state': os.path.join(d, 'optimizer.tar'), 'stats': self.stats[-1:] or []}
+        if self.validate:
+            infos['best_elites'] = [[p, s] for p, s in self.best_elites]
         name = 'z_info_e{e}_i{i}-{n}.json'.format(e=self.sched.epoch, i=self.sched.iteration, n=0)
         with open(os.path.join(d, name), 'w') as f:
             json.dump(infos, f)

@@ -199,6 +199,12 @@ class EnginePolicy:
         fit = self.e.evaluate_theta(0, iteration=self.eval_iteration())
         return float(fit[0].item())
 
+    def accuracy_on(self, validator, config=None, directory=None):
+        """CaptPolicy.accuracy_on (policies.py:130-143): the CIDEr of eval_split of the current theta on the
+        validator's split (nicnes.validation.Validator: the greedy decode and COCOEvalCap's metrics on the GPU)."""
+        lang_stats, _ = validator.eval_split()
+        return float(lang_stats['CIDEr'])
+
 
 # ---------------------------------------------------------------- worker --------------------------
 class EngineWorker:

@@ -193,7 +193,7 @@ def chunk_evals(rs, chunk, eval_prob):
 
 
 def run_reference_worker(client, worker, chunk=16, eval_prob=0.0, max_tasks=None, stop=None, seed=None,
-                         idle_sleep=0.005, max_results=None, retry_sleep=0.05, own_batches=None):
+                         idle_sleep=0.005, max_results=None, retry_sleep=0.05, own_batches=None, validator=None):
     """NESWorker.run_worker (nic_nes_worker.py:41-90) against a reference master: `client` is a
     nicnes.transport.WorkerClient built with codec=RefPickleCodec. Each pass takes `chunk` slots:
     chunk_evals of them are eval results (one rollout of the unperturbed theta, pushed once per eval
@@ -202,8 +202,10 @@ def run_reference_worker(client, worker, chunk=16, eval_prob=0.0, max_tasks=None
     task keep flowing until the master declares the next one, as reference workers do (surplus results
     are dropped by the master, nic_nes_master.py:108-116). A missing or half-written parameter file is
     logged and the task re-read, as nic_nes_worker.py:71-84 does. With single_batch: false and own_batches (an
-    OwnBatches), each member slot draws its batch from it at the task's batch_size. Returns the number of
-    tasks seen."""
+    OwnBatches), each member slot draws its batch from it at the task's batch_size. validator (a
+    nicnes.validation.Validator on the worker's engine): an eval result then carries the validation CIDEr of the
+    task's theta (NESWorker.accuracy, nic_nes_worker.py:99-113) instead of the training batch's fitness. Returns the
+    number of tasks seen."""
     rs = random.Random(seed)
     log = logging.getLogger(__name__)
     spec = getattr(worker, 'spec', None)
@@ -222,7 +224,10 @@ def run_reference_worker(client, worker, chunk=16, eval_prob=0.0, max_tasks=None
         try:
             if n_eval:
                 worker._prepare(task_id, task)
-                score = worker.policy.rollout(None, task.batch_data, None)
+                if validator is not None:
+                    score = worker.policy.accuracy_on(validator)
+                else:
+                    score = worker.policy.rollout(None, task.batch_data, None)
                 ev = RefNESResult(worker_id=worker.worker_id, eval_score=score, mem_usage=_rss())
                 client.push_results(task_id, [ev] * n_eval)
                 pushed += n_eval

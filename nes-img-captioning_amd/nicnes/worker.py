@@ -55,6 +55,10 @@ def parse_args(argv=None):
     ap.add_argument('--max_tasks', type=int, default=None)
     ap.add_argument('--data_root', default='.', help="directory the experiment's caption_options paths are "
                                                      "relative to (the reference runs from src/)")
+    ap.add_argument('--validate', action='store_true',
+                    help="reference wire: eval results carry the validation CIDEr of the task's theta on the first "
+                         "config.num_val_items images of the 'val' split of the experiment's caption_options "
+                         "(default: the training batch's fitness)")
     return ap.parse_args(argv)
 
 
@@ -132,8 +136,15 @@ def worker_main(index, device, args, shared_device=False):
                                    spec.batch_size)
             except FileNotFoundError as e:
                 logging.warning('no caption data for an own loader (%s)', e)
+        validator = None
+        if getattr(args, 'validate', False):
+            from nicnes import data as Dt
+            from nicnes.validation import Validator
+            loader = Dt.loader_from_caption_options(spec.exp, spec.batch_size, seed=0, root=args.data_root)
+            num = spec.config.num_val_items
+            validator = Validator(engine, loader, 'val', 5000 if num is None else int(num))
         W.run_reference_worker(client, worker, chunk=args.chunk, eval_prob=eval_prob, stop=stop,
-                               max_tasks=args.max_tasks, own_batches=own)
+                               max_tasks=args.max_tasks, own_batches=own, validator=validator)
     else:
         M.run_worker(client, worker, chunk=args.chunk, stop=stop, max_tasks=args.max_tasks)
     stop.set()
