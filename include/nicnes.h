@@ -373,7 +373,7 @@ int nicnes_last_decode_lse(nicnes_handle* h, int32_t* bounded_host);
 /* Screened decode (not a reference interface): mode 1 runs the logit loop of the fused greedy-only decode
  * (128-row slabs, one workgroup per member slab, pair-bounded lse, no log-probs, plain mutations) in bf16 and certifies
  * the candidate tokens it leaves with exact fp32 chains; mode 0 the fp32 loop; mode 2 (the default) screens when the
- * decode has more workgroups (members x slabs) than the GPU has CUs, where it is faster. Tokens do not depend on it.
+ * decode has at least as many workgroups (members x slabs) as the GPU has CUs, where it is faster. Tokens do not depend on it.
  * env NICNES_SCREEN=0/1/2 sets the initial value; test hook NICNES_SCREEN_EPS_SCALE (>= 1) widens the screening bound. */
 int nicnes_set_decode_screen(nicnes_handle* h, int32_t mode);
 /* the screened decodes' counters since create: [0] candidate ids captured, [1] rows that sent their
@@ -388,6 +388,17 @@ int nicnes_screen_stats(nicnes_handle* h, int64_t* out2_host);
  * only. Asynchronous on stream. */
 int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
                             const float* h_rows_dev, float* out_mfma_dev, float* out_chain_dev, void* stream);
+/* Test entry (no reference counterpart): given candidates through the screened decode's cooperative certify (DESIGN.md
+ * 5). h_rows_dev [128, 128] fp32 (unit order) is laid out as the lane scratch of one decode workgroup's eight waves;
+ * items_host [n_items, 2] int32 (HOST) holds (row in [0, 128), vocabulary id in [0, vocab_size]) pairs in any order,
+ * repeats allowed. Each item is owned by the thread the decode gives that row of `sign` and goes through the same work
+ * queue, coalesced row staging, fmaf chain and result slots as a decode's candidates; out_dev [n_items] fp32 receives
+ * each item's exact logit of member `member` of `iteration` at sigma, bit for bit nicnes_test_logit_chain's. A row or
+ * an id out of range is NICNES_ERR_INVALID and nothing runs. No decode may run beside it. Plain mutations only.
+ * Synchronises the stream. */
+int nicnes_test_certify_items(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
+                              const float* h_rows_dev, const int32_t* items_host, int32_t n_items, float* out_dev,
+                              void* stream);
 /* Test entry (no reference counterpart): the scorer of nicnes_evaluate* on GIVEN token rows instead of a decode's, so a
  * test can choose the hypotheses (caption lengths, repeats, ids at the key packing's top bit) that a decode of a random
  * theta never emits. seq_dev [n_cand, rows, seq_length] int32; candidates 2k and 2k + 1 are member k's, scored on batch

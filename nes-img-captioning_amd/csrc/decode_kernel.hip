@@ -1117,10 +1117,11 @@ __device__ __forceinline__ void sample_pick(const DecodeParams& p, rsrc_t lr, ui
 // tie_window's outer half-ulp). ScreenStage keeps the screened max and pair-bounded exp-sum as epilogue64<PAIRS> does
 // and leaves one word per lane and stage in the workgroup's capture slot: the largest of the lane's 16 pair maxima
 // with its low five mantissa bits replaced by the pair's index (bits 0-3) and a crowded flag (bit 4: a second pair
-// maximum within `delta` of it, delta >= 2 eps + hu_out). After the loop screen_certify scans the lane's words against
-// the final threshold and computes the exact logits of the ids behind each hit (the pair, or all 32 of a crowded
-// lane-stage) with logit_chain, in id order, into the same records the fp32 loop keeps. A step the records cannot
-// decide is run again by the fp32 loop itself (step_body).
+// maximum within `delta` of it, delta >= 2 eps + hu_out). After the loop screen_scan lists the lane's words that reach
+// the final threshold, and certify_queue, the whole workgroup over one queue of the lists' ids (the pair behind a hit,
+// or all 32 ids of a crowded lane-stage), computes their exact logits with logit_chain's arithmetic; each lane takes
+// its own in id order into the same records the fp32 loop keeps. A step the records cannot decide is run again by the
+// fp32 loop itself (step_body).
 #define SCREEN_PACK_REL 1.52587890625e-05f   // 2^-16: the word is within 2^-18 |q| of the pair maximum it encodes
 #define SCREEN_HU_MAX 1.9073486328125e-06f   // 2^-19: tie_window's hu_out while lse < 64
 #define SCREEN_HIT_CAP 8                     // hit lane-stages one lane certifies (a crowded one counts 4); more: the fp32 loop
@@ -1178,13 +1179,27 @@ __device__ __forceinline__ void record1(RowState& st, float L, int v) {
     st.r1i = c ? v : st.r1i;
 }
 
+// Chunk (T, c) of a row's exact logit chain: acc = fmaf(w_k, h_k, acc) over the 8 units 32T + 8c .. + 7 in the order
+// the MFMA chains consume them (nn_kperm: MFMA 16T + jj takes k = 32T + 8(jj / 4) + jj % 4 from lane half 0, then
+// that + 4 from half 1), a0 = w of units 32T + 8c .. + 3, a1 = the next four. h comes from lane scratch as the cell
+// left it: H_SLOT(i) of lane half hh holds unit nn_kperm(2 i + hh) of the row at row_lo, the partner half 128 bytes on.
+__device__ __forceinline__ float chain_chunk(float acc, const f32x4& a0, const f32x4& a1, rsrc_t scr_r, uint32_t row_lo,
+                                             int T, int c) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        // slot 16T + 4c + e: unit 32T + 8c + e in lane half 0, that + 4 in half 1
+        const uint32_t so = H_SLOT_BYTES + 256u * (uint32_t)(16 * T + 4 * c + e);
+        acc = __builtin_fmaf(a0[e], ld1(scr_r, row_lo, so), acc);
+        acc = __builtin_fmaf(a1[e], ld1(scr_r, row_lo + 128u, so), acc);
+    }
+    return acc;
+}
+
 // One lane's exact logit of vocabulary id v for the row at row_lo = 4 * (lane & 31) of the wave's lane scratch: the
-// fp32 chain acc = fmaf(w_k, h_k, acc) from the bias, with w = fp32(W0 +/- delta) formed as the staging forms it and k
-// in the order the MFMA chains consume it (nn_kperm: MFMA 16T + jj takes k = 32T + 8(jj / 4) + jj % 4 from lane half 0,
-// then that + 4 from half 1). h comes from the scratch as the cell left it: H_SLOT(i) of lane half hh holds unit
-// nn_kperm(2 i + hh) of the row, the partner half 128 bytes on. The fp32 MFMA is that fmaf chain bit for bit, so this
-// equals mfma_tile's and mfma_stage64_o's accumulator for (v, row) without staging a tile; the test entry below runs
-// this function against mfma_tile over the whole vocabulary (tests/test_gpu_screen.py).
+// fp32 chain from the bias (chain_chunk), with w = fp32(W0 +/- delta) formed as the staging forms it. The fp32 MFMA is
+// that fmaf chain bit for bit, so this equals mfma_tile's and mfma_stage64_o's accumulator for (v, row) without
+// staging a tile; the test entry below runs this function against mfma_tile over the whole vocabulary
+// (tests/test_gpu_screen.py). The screened decode runs the same chain from rows staged in LDS (chain_lds).
 __device__ __forceinline__ float logit_chain(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, int v, int sgn,
                                                  rsrc_t scr_r, uint32_t row_lo) {
     const uint32_t wo = 4u * ((uint32_t)p.off_log_w + 128u * (uint32_t)v), bo = 4u * ((uint32_t)p.off_log_b + (uint32_t)v);
@@ -1198,28 +1213,37 @@ __device__ __forceinline__ float logit_chain(const DecodeParams& p, rsrc_t theta
             const f32x4 w0 = ld4(theta_r, wo + ko), z0 = ld4(noise_r, wo + ko);
             const f32x4 w1 = ld4(theta_r, wo + ko + 16u), z1 = ld4(noise_r, wo + ko + 16u);
             const f32x4 a0 = sgn ? w0 - z0 : w0 + z0, a1 = sgn ? w1 - z1 : w1 + z1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                // slot 16T + 4c + e: unit 32T + 8c + e in lane half 0, that + 4 in half 1
-                const uint32_t so = H_SLOT_BYTES + 256u * (uint32_t)(16 * T + 4 * c + e);
-                acc = __builtin_fmaf(a0[e], ld1(scr_r, row_lo, so), acc);
-                acc = __builtin_fmaf(a1[e], ld1(scr_r, row_lo + 128u, so), acc);
-            }
+            acc = chain_chunk(acc, a0, a1, scr_r, row_lo, T, c);
         }
     }
     return acc;
 }
 
-// The lane's words against thr (already lowered by the packing error): exact logits of the ids behind every hit into
-// st's records. Returns false when the lane would certify more than SCREEN_HIT_CAP lane-stages (the step goes to the
-// fp32 loop). ncand counts the candidate ids captured.
-__device__ __forceinline__ bool screen_certify(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, rsrc_t scr_r,
-                                               rsrc_t cap, uint32_t vo, int nst, int sgn, int hh, uint32_t row_lo,
-                                               float thr, float* lds, int tid, RowState& st, int& ncand) {
-    // pass 1: the lane's hit lane-stages, in stage order, into its private list in LDS (free between the logit loop's
-    // last barrier and the token phase's): entry = stage << 8 | crowded << 4 | pair
+// The same chain with w and the bias start value read from a row staged in LDS (certify_queue: LDS_ROW floats, the
+// bias in the first pad word)
+__device__ __forceinline__ float chain_lds(const float* wrow, rsrc_t scr_r, uint32_t row_lo) {
+    float acc = wrow[128];
+#pragma unroll
+    for (int T = 0; T < 4; ++T) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(wrow + 32 * T + 8 * c);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(wrow + 32 * T + 8 * c + 4);
+            acc = chain_chunk(acc, a0, a1, scr_r, row_lo, T, c);
+        }
+    }
+    return acc;
+}
+
+// Pass 1 of the certify: the lane's words against thr (already lowered by the packing error); its hit lane-stages, in
+// stage order, go into its private list in LDS (free between the logit loop's last barrier and the token phase's):
+// entry = stage << 8 | crowded << 4 | pair. cnt: the entries listed; ncand counts the candidate ids captured. Returns
+// false when the lane would certify more than SCREEN_HIT_CAP lane-stages (the step goes to the fp32 loop).
+__device__ __forceinline__ bool screen_scan(rsrc_t cap, uint32_t vo, int nst, float thr, float* lds, int tid, int& cnt,
+                                            int& ncand) {
     uint32_t* list = reinterpret_cast<uint32_t*>(lds) + tid * SCREEN_HIT_CAP;
-    int cnt = 0, hits = 0;
+    int hits = 0;
+    cnt = 0;
     for (int s0 = 0; s0 < nst; s0 += 16) {
         uint32_t wd[16];
 #pragma unroll
@@ -1236,11 +1260,16 @@ __device__ __forceinline__ bool screen_certify(const DecodeParams& p, rsrc_t the
             }
         }
     }
-    if (hits > SCREEN_HIT_CAP) return false;
-    // pass 2: hit k of every lane at once (the wave runs as many rounds as its busiest lane has hits)
-    for (int k = 0; k < SCREEN_HIT_CAP; ++k) {
-        if (!__any(k < cnt)) break;
-        if (k < cnt) {
+    return hits <= SCREEN_HIT_CAP;
+}
+
+// the ids behind a lane's listed hits (the pair, or all 32 of a crowded lane-stage), in increasing order
+struct ListItems {
+    const uint32_t* list;
+    int cnt, hh, V1;
+    template <class F>
+    __device__ __forceinline__ void operator()(F&& f) const {
+        for (int k = 0; k < cnt; ++k) {
             const uint32_t e = list[k];
             const int s = (int)(e >> 8), pr = (int)(e & 15u);
             const bool crowded = (e & 16u) != 0;
@@ -1249,13 +1278,112 @@ __device__ __forceinline__ bool screen_certify(const DecodeParams& p, rsrc_t the
             for (int i = i0; i < i1; ++i) {
                 const int a = i & 15;
                 const int v = 64 * s + 32 * (i >> 4) + 4 * hh + (a & 3) + 8 * (a >> 2);
-                if (v < p.V1) {
-                    record1(st, logit_chain(p, theta_r, noise_r, v, sgn, scr_r, row_lo), v);
-                }
+                if (v < V1) f(v);
             }
         }
     }
-    return true;
+};
+
+// Pass 2 of the certify, by the whole workgroup (every thread calls it, with or without items). The threads' items
+// (owner thread, vocabulary id) are numbered owner by owner with a wave scan and one cross-wave prefix through LDS and
+// written to a queue in LDS; the queue is worked off in batches of CERT_BATCH items and rounds of CERT_ROWS: the 32-lane
+// groups stage one candidate row per item (one ld4 of theta and one of the noise per lane, a full 512-byte line each;
+// fp32(W0 +/- delta) as logit_chain forms it, the bias start value in the row's pad), then thread j runs item j's
+// chain from its staged row (chain_lds; h from the owner's lane scratch) into the item's result slot. After a batch
+// each owner takes its results in item order. So the rounds of a step are its items over CERT_ROWS, whichever lanes
+// own them. each(f) calls f(id) for the thread's n_mine items in order; sink(L, id) receives them in the same order.
+// wscr_r: the lane scratch of the workgroup's eight waves. LDS (floats): the lists | 8 wave totals | queue | results |
+// rows. pm: DECODE_PROF slots of the step (CERT_PROF_AT(t) + 1; < 0: none): queue built, first round's rows staged,
+// chains done.
+#define CERT_PROF_AT(t) (640 + 5 * ((t) + 1))   // + 0 scan done .. + 4 records fed (beyond the step marks of T <= 20)
+#define CERT_ROWS 192
+#define CERT_BATCH (8 * CERT_ROWS)
+#define CERT_TOT_AT (NTHREADS * SCREEN_HIT_CAP)
+#define CERT_QUEUE_AT (CERT_TOT_AT + 16)
+#define CERT_RES_AT (CERT_QUEUE_AT + CERT_BATCH)
+#define CERT_ROWS_AT (CERT_RES_AT + CERT_BATCH)
+static_assert(CERT_ROWS_AT % 4 == 0 && CERT_ROWS_AT + CERT_ROWS * LDS_ROW <= 2 * STAGE64_FLOATS, "certify LDS layout");
+#define CERT_ID_BITS 23                      // item = owner thread << 23 | id (bit 31: the owner's sign)
+template <class Each, class Sink>
+__device__ __forceinline__ void certify_queue(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, rsrc_t wscr_r,
+                                              float* lds, int tid, int n_mine, const Each& each, Sink&& sink, int pm) {
+    uint32_t* lw = reinterpret_cast<uint32_t*>(lds);
+    float* rows = lds + CERT_ROWS_AT;
+    const int lane = tid & 63, wave = tid >> 6;
+    int inc = n_mine;                                        // inclusive scan over the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int u = __shfl_up(inc, d);
+        inc += lane >= d ? u : 0;
+    }
+    if (lane == 63) lw[CERT_TOT_AT + wave] = (uint32_t)inc;
+    __syncthreads();
+    int first = inc - n_mine, total = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) {
+        const int c = (int)lw[CERT_TOT_AT + w];
+        first += w < wave ? c : 0;
+        total += c;
+    }
+    for (int b0 = 0; b0 < total; b0 += CERT_BATCH) {
+        const int nb = min(CERT_BATCH, total - b0);
+        const bool mine = first < b0 + nb && first + n_mine > b0;     // some of the thread's items are in this batch
+        if (mine) {
+            int pos = first - b0;
+            each([&](int v) {
+                if ((unsigned)pos < (unsigned)nb) lw[CERT_QUEUE_AT + pos] = ((uint32_t)tid << CERT_ID_BITS) | (uint32_t)v;
+                ++pos;
+            });
+        }
+        __syncthreads();
+        if (pm >= 0) PROF_MARK(pm + 0);
+        for (int r0 = 0; r0 < nb; r0 += CERT_ROWS) {
+            const int nr = min(CERT_ROWS, nb - r0);
+            const int q = tid & 31, g = tid >> 5;
+            for (int j0 = 0; j0 < nr; j0 += 64) {            // 16 groups x 4 rows in flight
+                f32x4 w[4], z[4];
+                float bw[4], bz[4];
+                uint32_t it[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    it[u] = lw[CERT_QUEUE_AT + r0 + min(j0 + g + 16 * u, nr - 1)];
+                    const uint32_t v = it[u] & ((1u << CERT_ID_BITS) - 1u);
+                    const uint32_t wo = 4u * ((uint32_t)p.off_log_w + 128u * v) + 16u * (uint32_t)q;
+                    const uint32_t bo = 4u * ((uint32_t)p.off_log_b + v);
+                    w[u] = ld4(theta_r, wo);
+                    z[u] = ld4(noise_r, wo);
+                    bw[u] = ld1(theta_r, bo);
+                    bz[u] = ld1(noise_r, bo);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int j = j0 + g + 16 * u;
+                    if (j < nr) {
+                        const bool sg = (it[u] >> 31) != 0;
+                        *reinterpret_cast<f32x4*>(rows + j * LDS_ROW + 4 * q) = sg ? w[u] - z[u] : w[u] + z[u];
+                        if (q == 0) rows[j * LDS_ROW + 128] = sg ? bw[u] - bz[u] : bw[u] + bz[u];
+                    }
+                }
+            }
+            __syncthreads();
+            if (pm >= 0 && r0 == 0) PROF_MARK(pm + 1);
+            if (tid < nr) {
+                const uint32_t item = lw[CERT_QUEUE_AT + r0 + tid];
+                const uint32_t owner = item >> CERT_ID_BITS;
+                const uint32_t row_lo = (owner >> 6) * (uint32_t)(SCR_SLOTS * 64 * 4) + 4u * (owner & 31u);
+                lds[CERT_RES_AT + r0 + tid] = chain_lds(rows + tid * LDS_ROW, wscr_r, row_lo);
+            }
+            __syncthreads();
+        }
+        if (pm >= 0) PROF_MARK(pm + 2);
+        if (mine) {
+            int pos = first - b0;
+            each([&](int v) {
+                if ((unsigned)pos < (unsigned)nb) sink(lds[CERT_RES_AT + pos], v);
+                ++pos;
+            });
+        }
+    }
 }
 
 // max_v |w_v|^2 and max_v |b_v| of a member's logit rows, both signs (ScreenArgs::norm): one workgroup per
@@ -1767,7 +1895,7 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_decode_img64_kernel(DecodePar
 // SAMPLE: the sampled decode (nets.py:210-231): the logit loop stores its logits and stage sums (SampleStage), then
 // sample_pick draws each row's token with its uniform p.sample_u (fused path only)
 // SCREEN (PAIRS, greedy only): the logit loop runs in bf16 and the candidates it leaves are certified by fp32 chains
-// (ScreenStage / screen_certify above); tokens are those of the fp32 loop
+// (ScreenStage / screen_scan / certify_queue above); tokens are those of the fp32 loop
 template <bool PAIRS, bool PREFETCH, bool SAMPLE = false, bool MUT = false, bool SCREEN = false>
 __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, float* lds, int t, Stage64Regs& s64,
                                           bool& pre, float (&hB)[64], bool& hpre, const MutRes* mr = nullptr,
@@ -1891,11 +2019,23 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
                 bool bad = p.force_exact || !(fabsf(thr) < 3.0e38f) || !(w.hu_out <= SCREEN_HU_MAX) || !(stot > 0.f);
                 st.r1v = st.r0v = st.ev = NEG_INF;
                 st.r1i = st.r0i = 0x7fffffff;
-                int ncand = 0;
-                if (need && !bad)
-                    bad = !screen_certify(p, c.theta_r, c.noise_r, c.scr_r, scap_r, 4u * (uint32_t)(c.wave * 64 + lane_fresh()),
-                                          nl, c.sgn, c.hh, 4u * (uint32_t)(lane_fresh() & 31), thr, lds,
-                                          c.wave * 64 + lane_fresh(), st, ncand);
+                int ncand = 0, ccnt = 0;
+                if (need && !bad) {
+                    bad = !screen_scan(scap_r, 4u * (uint32_t)(c.wave * 64 + lane_fresh()), nl, thr, lds,
+                                       c.wave * 64 + lane_fresh(), ccnt, ncand);
+                    if (bad) ccnt = 0;               // over the cap: nothing of this lane is certified
+                }
+                PROF_MARK(CERT_PROF_AT(t));
+                {
+                    const int ctid = c.wave * 64 + lane_fresh();
+                    const ListItems items{reinterpret_cast<const uint32_t*>(lds) + ctid * SCREEN_HIT_CAP, ccnt, c.hh, p.V1};
+                    int n_mine = 0;
+                    items([&](int) { ++n_mine; });
+                    const rsrc_t wscr_r = make_rsrc(p.scratch + (size_t)c.wg * 8 * (SCR_SLOTS * 64), 8 * SCR_SLOTS * 64 * 4);
+                    certify_queue(p, c.theta_r, c.noise_r, wscr_r, lds, ctid, n_mine, items,
+                                  [&](float L, int v) { record1(st, L, v); }, CERT_PROF_AT(t) + 1);
+                }
+                PROF_MARK(CERT_PROF_AT(t) + 4);
 #pragma unroll
                 for (int dd = 32; dd >= 1; dd >>= 1) ncand += __shfl_xor(ncand, dd);
                 if (ncand && lane_fresh() == 0) atomicAdd(sa->ctr, (unsigned long long)ncand);   // one atomic per wave and step
@@ -3363,6 +3503,43 @@ extern "C" hipError_t nicnes_launch_test_logit_chain(const DecodeParams* p, uint
     hipLaunchKernelGGL(nicnes_test_h_scratch_kernel, dim3(1), dim3(64), 0, stream, hin, p->scratch);
     hipLaunchKernelGGL(nicnes_test_logit_chain_kernel, dim3((p->V1 + 31) / 32), dim3(NTHREADS),
                        (size_t)STAGE_FLOATS * sizeof(float), stream, *p, nidx, sgn, out_mfma, out_chain);
+    return hipGetLastError();
+}
+
+// ========== test entry: given (row, id) items through the screened decode's certify_queue ======================
+// One workgroup of the decode's shape. hin [128, 128] is laid out as its eight waves' lane scratch (wave w: sign w >> 2,
+// rows 32 (w & 3) .. + 31, both signs the same rows); the items, grouped by row (row_start [129], ids and their
+// positions in the caller's list), are owned by the thread the decode gives that row of sign sgn, and each item's
+// logit lands at its position in out.
+__global__ __launch_bounds__(NTHREADS) void nicnes_test_certify_kernel(DecodeParams p, uint64_t nidx, int sgn,
+                                                                       const int32_t* row_start, const int32_t* ids,
+                                                                       const int32_t* pos_of, float* out) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const rsrc_t theta_r = make_rsrc(p.theta, 4u * (uint32_t)p.D);
+    const rsrc_t noise_r = make_rsrc(p.noise + nidx, 4u * (uint32_t)p.D);
+    const rsrc_t wscr_r = make_rsrc(p.scratch, 8 * SCR_SLOTS * 64 * 4);
+    const bool owner = (wave >> 2) == sgn && lane < 32;
+    const int row = 32 * (wave & 3) + (lane & 31);
+    const int i0 = owner ? row_start[row] : 0, i1 = owner ? row_start[row + 1] : 0;
+    auto each = [&](auto&& f) {
+        for (int i = i0; i < i1; ++i) f(ids[i]);
+    };
+    int k = i0;
+    certify_queue(p, theta_r, noise_r, wscr_r, lds, tid, i1 - i0, each, [&](float L, int) { out[pos_of[k++]] = L; }, -1);
+}
+
+extern "C" hipError_t nicnes_launch_test_certify_items(const DecodeParams* p, uint64_t nidx, int sgn, const float* hin,
+                                                       const int32_t* row_start, const int32_t* ids,
+                                                       const int32_t* pos_of, float* out, hipStream_t stream) {
+    hipError_t e = hipFuncSetAttribute((const void*)nicnes_test_certify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)LDS64);
+    if (e != hipSuccess) return e;
+    for (int w = 0; w < 8; ++w)
+        hipLaunchKernelGGL(nicnes_test_h_scratch_kernel, dim3(1), dim3(64), 0, stream, hin + (size_t)(w & 3) * 32 * 128,
+                           p->scratch + (size_t)w * SCR_SLOTS * 64);
+    hipLaunchKernelGGL(nicnes_test_certify_kernel, dim3(1), dim3(NTHREADS), LDS64, stream, *p, nidx, sgn, row_start, ids,
+                       pos_of, out);
     return hipGetLastError();
 }
 

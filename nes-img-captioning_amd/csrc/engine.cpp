@@ -1095,9 +1095,10 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     if ((int64_t)count * nslabs * S > h->part_cap)
         return fail(h, NICNES_ERR_INVALID, "decode split beyond the partial-state buffer (nicnes_set_decode_split)");
     ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr};
-    // automatic: with one workgroup per CU or fewer the launch lasts as long as its slowest workgroup, and the screened
-    // decode's workgroup times spread widely (P = 256, B = 128: 23.6 ms against 22.95 ms unscreened)
-    const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)count * nslabs > h->n_cu);
+    // automatic: from one workgroup per CU on (P = 256, B = 128: 15.7 ms an iteration screened against 23.05 ms
+    // unscreened; with the certify spread over the workgroup a launch of one round of workgroups no longer
+    // waits on a slow one). Fewer workgroups than CUs: not measured, the fp32 loop as before
+    const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)count * nslabs >= h->n_cu);
     if (screen_on && !sampled && !p.lp && bounded && G == 4 && S == 1 && !(h->mut_mode && !eval_theta)) {
         // the screened logit loop: a capture slot per workgroup and the members' norms (ensure_screen, at create or
         // at the setter: nothing is allocated here); a decode of more workgroups than slots runs the fp32 loop
@@ -1407,7 +1408,7 @@ static int split_decode_impl(nicnes_handle* h, nicnes_split* sp, int32_t first, 
     const bool bounded = h->bounded_mode == 1 || (h->bounded_mode == 2 && h->exact_left == 0);
     p.bounded_lse = bounded ? 1 : 0;
     ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr};
-    const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)n_pm * nslabs > h->n_cu);
+    const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)n_pm * nslabs >= h->n_cu);
     if (screen_on && !p.lp && bounded && G == 4 && S == 1 && h->screen_cap && h->screen_norm &&
         (int64_t)n_pm * nslabs <= h->screen_wgs && n_pm <= h->cfg.max_members) {
         sa.cap = h->screen_cap;
@@ -1852,6 +1853,64 @@ int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member
     p.scratch = h->dscratch;        // one wave's lane scratch holds the rows of h (no decode runs beside this)
     const uint64_t nidx = nn_noise_index(h->cfg.noise_seed, iteration, (uint64_t)member, h->cfg.noise_len, (uint64_t)h->D);
     HIPC(h, nicnes_launch_test_logit_chain(&p, nidx, sign, h_rows, out_mfma, out_chain, s));
+    return NICNES_OK;
+}
+
+int nicnes_test_certify_items(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
+                              const float* h_rows, const int32_t* items_host, int32_t n_items, float* out, void* stream) {
+    if (!h || !h_rows || n_items < 0 || (n_items && (!items_host || !out)) || member < 0 || (sign != 0 && sign != 1))
+        return NICNES_ERR_INVALID;
+    if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
+    if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
+    if (h->mut_mode) return fail(h, NICNES_ERR_UNSUPPORTED, "nicnes_test_certify_items: plain mutations only");
+    for (int32_t i = 0; i < n_items; ++i) {
+        const int32_t row = items_host[2 * i], id = items_host[2 * i + 1];
+        if (row < 0 || row >= 128) return fail(h, NICNES_ERR_INVALID, "nicnes_test_certify_items: row outside [0, 128)");
+        if (id < 0 || id >= h->V1) return fail(h, NICNES_ERR_INVALID, "nicnes_test_certify_items: id outside [0, vocab_size]");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    if (!h->noise_sc) {
+        HIPC(h, hipDeviceSynchronize());
+        int rc = dalloc(h, &h->noise_sc, (size_t)h->cfg.noise_len);
+        if (rc) return rc;
+    }
+    if (!h->sc_valid || __builtin_bit_cast(uint32_t, h->sc_sigma) != __builtin_bit_cast(uint32_t, sigma)) {
+        HIPC(h, nicnes_launch_scale(h->noise, h->noise_sc, h->cfg.noise_len, sigma, s));
+        h->sc_sigma = sigma;
+        h->sc_valid = true;
+    }
+    // the items grouped by row, in the caller's order inside a row: row_start [129] | ids [n] | positions [n]
+    std::vector<int32_t> host(129 + 2 * (size_t)n_items, 0);
+    int32_t* row_start = host.data();
+    int32_t* ids = row_start + 129;
+    int32_t* pos_of = ids + n_items;
+    for (int32_t i = 0; i < n_items; ++i) ++row_start[items_host[2 * i] + 1];
+    for (int r = 0; r < 128; ++r) row_start[r + 1] += row_start[r];
+    std::vector<int32_t> fill(row_start, row_start + 128);
+    for (int32_t i = 0; i < n_items; ++i) {
+        const int32_t at = fill[items_host[2 * i]]++;
+        ids[at] = items_host[2 * i + 1];
+        pos_of[at] = i;
+    }
+    int32_t* dev = nullptr;
+    HIPC(h, hipMalloc((void**)&dev, host.size() * sizeof(int32_t)));
+    hipError_t e = hipMemcpyAsync(dev, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    DecodeParams p{};
+    p.theta = h->theta32;
+    p.noise = h->noise_sc;
+    p.V1 = h->V1;
+    p.D = h->D;
+    p.off_log_w = h->off[3];
+    p.off_log_b = h->off[4];
+    p.scratch = h->dscratch;        // eight waves' lane scratch hold the rows of h (no decode runs beside this)
+    const uint64_t nidx = nn_noise_index(h->cfg.noise_seed, iteration, (uint64_t)member, h->cfg.noise_len, (uint64_t)h->D);
+    if (e == hipSuccess)
+        e = nicnes_launch_test_certify_items(&p, nidx, sign, h_rows, dev, dev + 129, dev + 129 + n_items, out, s);
+    const hipError_t e2 = hipStreamSynchronize(s);    // host and dev live until the kernel has read them
+    (void)hipFree(dev);
+    HIPC(h, e);
+    HIPC(h, e2);
     return NICNES_OK;
 }
 

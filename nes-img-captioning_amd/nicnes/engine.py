@@ -418,7 +418,7 @@ class Engine:
 
     def set_decode_screen(self, on):
         """The bf16-screened logit loop of the fused greedy-only decode on (True), off (False) or 'auto' (the default:
-        on when members x slabs exceed the CU count). Tokens do not depend on it."""
+        on when members x slabs reach the CU count). Tokens do not depend on it."""
         mode = 2 if (isinstance(on, str) and on == 'auto') else int(bool(on))
         check(self.L.nicnes_set_decode_screen(self.h, mode), self.h, 'set_decode_screen')
 
@@ -435,6 +435,20 @@ class Engine:
                   'test_logit_chain')
             torch.cuda.current_stream().synchronize()   # hr stays alive until the kernel has read it
         return om, oc
+
+    def test_certify_items(self, iteration, member, sigma, sign, h_rows, items):
+        """Test entry: items [n, 2] of (row < 128, vocabulary id) over h_rows [128, 128] through the screened decode's
+        cooperative certify; an fp32 tensor [n] of their exact logits. An id or row out of range raises."""
+        hr = torch.as_tensor(h_rows, dtype=torch.float32, device=self.device).contiguous()
+        assert hr.shape == (128, self.cfg.rnn_size)
+        it = np.ascontiguousarray(np.asarray(items, dtype=np.int32).reshape(-1, 2))
+        n = int(it.shape[0])
+        out = torch.empty((max(n, 1),), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_test_certify_items(self.h, ctypes.c_uint64(iteration), int(member), ctypes.c_float(sigma),
+                                                   int(sign), _ptr(hr), it.ctypes.data_as(ctypes.c_void_p), n, _ptr(out),
+                                                   self._stream()), self.h, 'test_certify_items')
+        return out[:n]
 
     def test_score_rows(self, seq, member_batch=None, lp=None, base=None):
         """Test entry: the evaluate's scorer on given token rows. seq [n_cand, rows, seq_length] int; member_batch

@@ -32,11 +32,12 @@ def launch_spans(k, seq):
         for c_, d_ in zip(hw[:, sl], dur):
             per_cu[c_] = per_cu.get(c_, 0.0) + d_
         busy = np.array(list(per_cu.values()))
-        rows.append((name, st.min() / 100.0, span, dur.mean(), dur.min(), dur.max(), len(per_cu),
+        rows.append((name, st.min() / 100.0, span, dur.mean(), np.median(dur), dur.min(), dur.max(), len(per_cu),
                      busy.mean(), busy.max(), busy.mean() / span, ghz))
-    print(k, 'launch: start_us span_us wg_mean wg_min wg_max n_cu cu_busy_mean cu_busy_max eff(mean busy/span) GHz')
+    print(k, 'launch: start_us span_us wg_mean wg_median wg_min wg_max n_cu cu_busy_mean cu_busy_max '
+          'eff(mean busy/span) GHz')
     for r in sorted(rows, key=lambda r: r[1]):
-        print('%-8s %9.1f %8.1f %8.1f %8.1f %8.1f %4d %8.1f %8.1f %6.3f %5.2f' % r)
+        print('%-8s %9.1f %8.1f %8.1f %8.1f %8.1f %8.1f %4d %8.1f %8.1f %6.3f %5.2f' % r)
 
 
 def cell_stages(k, seq):
@@ -69,6 +70,32 @@ def cell_stages(k, seq):
             sp['l1_to_l2'].append(np.median(((ts[:, b + 23] - ts[:, b + 22]) % (1 << 32)) / 100.0))
             sp['l2_to_cell'].append(np.median(((ts[:, b + 1] - ts[:, b + 23]) % (1 << 32)) / 100.0))
         print(k, 'sampled token phase (us):', ' '.join('%s %.1f' % (n, np.median(v)) for n, v in sp.items()))
+
+
+def certify_phases(k, seq):
+    """DECODE_PROF=1 build, screened step launches: the certify of step t split at the marks CERT_PROF_AT(t) =
+    640 + 5 (t + 1) + {0: scan done, 1: queue built, 2: first round's rows staged, 3: chains done, 4: records fed}
+    (thread 0's clock; 1-3 only in a workgroup step with items), from the end of the logit loop (120 + 24 (t + 1)):
+    mean / median / max over workgroups, us."""
+    raw = seq.reshape(-1, 4096).cpu().numpy().astype(np.int64) & 0xffffffff
+    ts = raw[:, :1024]
+    if not ts[:, 640 + 5 * 2].any():
+        return                                                # not the screened kernel
+    print(k, 'certify t: wgs_with_items | scan | queue | first_rows | chains(all rounds) | records | whole  '
+          '(mean/median/max us over workgroups)')
+    for t in range(1, 17):
+        c = 640 + 5 * (t + 1)
+        b = ts[:, 120 + 24 * (t + 1)]
+        d = lambda x, y: ((x - y) % (1 << 32)) / 100.0
+        whole = d(ts[:, c + 4], ts[:, c])
+        # (seq is not cleared between evaluates: marks 1-3 of an earlier evaluate lie outside this step's certify)
+        has = (d(ts[:, c + 1], ts[:, c]) <= whole) & (d(ts[:, c + 3], ts[:, c]) <= whole) & \
+              (d(ts[:, c + 1], ts[:, c]) <= d(ts[:, c + 3], ts[:, c]))
+        f = lambda v: '%.1f/%.1f/%.1f' % (v.mean(), np.median(v), v.max()) if v.size else '-'
+        print('%s t=%-2d %4d | %s | %s | %s | %s | %s | %s' % (
+            k, t, int(has.sum()), f(d(ts[:, c], b)), f(d(ts[has, c + 1], ts[has, c])),
+            f(d(ts[has, c + 2], ts[has, c + 1])), f(d(ts[has, c + 3], ts[has, c + 2])),
+            f(d(ts[has, c + 4], ts[has, c + 3])), f(d(ts[:, c + 4], b))))
 
 
 def split_spans(k, seq, S=4):
@@ -204,6 +231,7 @@ def main():
             else:
                 launch_spans(k, seq)
                 cell_stages(k, seq)
+                certify_phases(k, seq)
     base = np.median(res['base'])
     out = {k: {'median_ms': round(float(np.median(v)), 3), 'min_ms': round(float(np.min(v)), 3),
                'vs_base': round(float(np.median(v) / base), 3),

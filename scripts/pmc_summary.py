@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402  (kernel_source_sha256: the profile records which decode sources it measured)
 
 
-def per_dispatch(root, kernel):
+def per_dispatch(root, kernel, drop_first=False):
     files = glob.glob(os.path.join(root, '**', '*counter_collection.csv'), recursive=True)
     if not files:
         raise SystemExit('no counter_collection.csv under %s' % root)
@@ -44,6 +44,8 @@ def per_dispatch(root, kernel):
         return {}
     gmax = max(d['grid'] for d in vals.values())
     keep = [vals[k]['c'] for k in sorted(vals) if vals[k]['grid'] == gmax]
+    if drop_first and len(keep) > 1:        # a run without warm-up: the first launch's GRBM window holds its set-up
+        keep = keep[1:]
     out = {}
     for name in keep[0]:
         xs = [c[name] for c in keep if name in c]
@@ -62,11 +64,13 @@ def main():
     ap.add_argument('--note', default='')
     ap.add_argument('--symbol', default=None, help='mangled name of the measured instantiation: the profile records '
                     'its machine-code hash in the tree\'s library (bench.load_pmc checks it)')
+    ap.add_argument('--drop-first', action='store_true', help='leave out the first full-grid dispatch of every pass '
+                    '(bench.py --warmup 0: its GRBM_GUI_ACTIVE counts the first launch\'s set-up)')
     ap.add_argument('--out', required=True)
     a = ap.parse_args()
     counters, dispatches = {}, {}
     for p in a.passes:
-        for name, (v, n) in per_dispatch(p, a.kernel).items():
+        for name, (v, n) in per_dispatch(p, a.kernel, a.drop_first).items():
             counters[name] = v
             dispatches[name] = n
     c = counters
