@@ -388,17 +388,24 @@ int nicnes_screen_stats(nicnes_handle* h, int64_t* out2_host);
  * only. Asynchronous on stream. */
 int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
                             const float* h_rows_dev, float* out_mfma_dev, float* out_chain_dev, void* stream);
-/* Test entry (no reference counterpart): given candidates through the screened decode's cooperative certify (DESIGN.md
+/* Test entry (no reference counterpart): given candidates through the screened decode's tile certify (DESIGN.md
  * 5). h_rows_dev [128, 128] fp32 (unit order) is laid out as the lane scratch of one decode workgroup's eight waves;
  * items_host [n_items, 2] int32 (HOST) holds (row in [0, 128), vocabulary id in [0, vocab_size]) pairs in any order,
- * repeats allowed. Each item is owned by the thread the decode gives that row of `sign` and goes through the same work
- * queue, coalesced row staging, fmaf chain and result slots as a decode's candidates; out_dev [n_items] fp32 receives
+ * repeats allowed. Each item is owned by the thread the decode gives that row of `sign` and goes through the same wave
+ * item list, row staging, fp32 MFMA tile and result words as a decode's candidates; out_dev [n_items] fp32 receives
  * each item's exact logit of member `member` of `iteration` at sigma, bit for bit nicnes_test_logit_chain's. A row or
  * an id out of range is NICNES_ERR_INVALID and nothing runs. No decode may run beside it. Plain mutations only.
  * Synchronises the stream. */
 int nicnes_test_certify_items(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
                               const float* h_rows_dev, const int32_t* items_host, int32_t n_items, float* out_dev,
                               void* stream);
+/* The same with the items' owners chosen: owner_by_id = 0 gives every item to lane half 0 of its row (as above); 1
+ * gives item (row, id) to lane row % 32 + 32 * ((id >> 2) & 1) of the row's wave, the lane a decode's hit lists put it
+ * behind, each lane's ids in increasing order. The certify's results cross lane halves through LDS in general; only
+ * this mode has owners in both. */
+int nicnes_test_certify_items_owned(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
+                                    int32_t owner_by_id, const float* h_rows_dev, const int32_t* items_host,
+                                    int32_t n_items, float* out_dev, void* stream);
 /* Test entry (no reference counterpart): the scorer of nicnes_evaluate* on GIVEN token rows instead of a decode's, so a
  * test can choose the hypotheses (caption lengths, repeats, ids at the key packing's top bit) that a decode of a random
  * theta never emits. seq_dev [n_cand, rows, seq_length] int32; candidates 2k and 2k + 1 are member k's, scored on batch

@@ -107,11 +107,11 @@ extern "C" hipError_t nicnes_launch_lp_batch_exit(const int32_t* seq, float* lp,
 // 32-row MFMA tile path and by the fmaf chain; reads theta, noise, scratch (one wave's lane scratch), V1, D, off_log_w, off_log_b of *p
 extern "C" hipError_t nicnes_launch_test_logit_chain(const DecodeParams* p, uint64_t nidx, int sgn, const float* hin,
                                                      float* out_mfma, float* out_chain, hipStream_t stream);
-// test entry (nicnes_test_certify_items): the items (grouped by row: row_start [129], ids, pos_of their positions in
-// out) of sign sgn over hin [128, 128] through the screened decode's certify queue, one workgroup; scratch holds eight
-// waves' lane scratch
+// test entry (nicnes_test_certify_items): the items (grouped by owner lane: lane_start [257], group 2 row + lane half;
+// ids, pos_of their positions in out) of sign sgn over hin [128, 128] through the screened decode's tile certify, one
+// workgroup; scratch holds eight waves' lane scratch
 extern "C" hipError_t nicnes_launch_test_certify_items(const DecodeParams* p, uint64_t nidx, int sgn, const float* hin,
-                                                       const int32_t* row_start, const int32_t* ids,
+                                                       const int32_t* lane_start, const int32_t* ids,
                                                        const int32_t* pos_of, float* out, hipStream_t stream);
 // lane scratch for up to member_count members x row_waves 32-row waves of one sign
 extern "C" size_t nicnes_decode_scratch_floats(int member_count, int row_waves_per_member);

@@ -241,17 +241,21 @@ __device__ __forceinline__ f32x16 bias_init(const float* bias, int hh) {
     return acc;
 }
 
+// k block T (units 32 T .. + 31) of mfma_tile; row: the lane's row and half of the tile
+__device__ __forceinline__ f32x16 mfma_tile_k(f32x16 acc, const float* row, const float (&Bop)[64], int T) {
+    f32x4 a[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) a[c] = *reinterpret_cast<const f32x4*>(row + T * 32 + 4 * c);
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[jj >> 2][jj & 3], Bop[16 * T + jj], acc, 0, 0, 0);
+    return acc;
+}
+
 __device__ __forceinline__ f32x16 mfma_tile(f32x16 acc, const float* w, const float (&Bop)[64], int lane) {
     const float* row = w + (lane & 31) * LDS_ROW + (lane >> 5) * 16;
 #pragma unroll
-    for (int T = 0; T < 4; ++T) {
-        f32x4 a[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) a[c] = *reinterpret_cast<const f32x4*>(row + T * 32 + 4 * c);
-#pragma unroll
-        for (int jj = 0; jj < 16; ++jj)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[jj >> 2][jj & 3], Bop[16 * T + jj], acc, 0, 0, 0);
-    }
+    for (int T = 0; T < 4; ++T) acc = mfma_tile_k(acc, row, Bop, T);
     return acc;
 }
 
@@ -1118,10 +1122,10 @@ __device__ __forceinline__ void sample_pick(const DecodeParams& p, rsrc_t lr, ui
 // and leaves one word per lane and stage in the workgroup's capture slot: the largest of the lane's 16 pair maxima
 // with its low five mantissa bits replaced by the pair's index (bits 0-3) and a crowded flag (bit 4: a second pair
 // maximum within `delta` of it, delta >= 2 eps + hu_out). After the loop screen_scan lists the lane's words that reach
-// the final threshold, and certify_queue, the whole workgroup over one queue of the lists' ids (the pair behind a hit,
-// or all 32 ids of a crowded lane-stage), computes their exact logits with logit_chain's arithmetic; each lane takes
-// its own in id order into the same records the fp32 loop keeps. A step the records cannot decide is run again by the
-// fp32 loop itself (step_body).
+// the final threshold, and certify_tiles, each wave over the ids behind its own lanes' lists (the pair behind a hit, or
+// all 32 ids of a crowded lane-stage), computes their exact logits on fp32 MFMA tiles (logit_chain's arithmetic bit for
+// bit); each lane takes its own in id order into the same records the fp32 loop keeps. A step the records cannot
+// decide is run again by the fp32 loop itself (step_body).
 #define SCREEN_PACK_REL 1.52587890625e-05f   // 2^-16: the word is within 2^-18 |q| of the pair maximum it encodes
 #define SCREEN_HU_MAX 1.9073486328125e-06f   // 2^-19: tie_window's hu_out while lse < 64
 #define SCREEN_HIT_CAP 8                     // hit lane-stages one lane certifies (a crowded one counts 4); more: the fp32 loop
@@ -1199,7 +1203,7 @@ __device__ __forceinline__ float chain_chunk(float acc, const f32x4& a0, const f
 // fp32 chain from the bias (chain_chunk), with w = fp32(W0 +/- delta) formed as the staging forms it. The fp32 MFMA is
 // that fmaf chain bit for bit, so this equals mfma_tile's and mfma_stage64_o's accumulator for (v, row) without
 // staging a tile; the test entry below runs this function against mfma_tile over the whole vocabulary
-// (tests/test_gpu_screen.py). The screened decode runs the same chain from rows staged in LDS (chain_lds).
+// (tests/test_gpu_screen.py). The screened decode certifies with the tile itself (certify_tiles).
 __device__ __forceinline__ float logit_chain(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, int v, int sgn,
                                                  rsrc_t scr_r, uint32_t row_lo) {
     const uint32_t wo = 4u * ((uint32_t)p.off_log_w + 128u * (uint32_t)v), bo = 4u * ((uint32_t)p.off_log_b + (uint32_t)v);
@@ -1213,22 +1217,6 @@ __device__ __forceinline__ float logit_chain(const DecodeParams& p, rsrc_t theta
             const f32x4 w0 = ld4(theta_r, wo + ko), z0 = ld4(noise_r, wo + ko);
             const f32x4 w1 = ld4(theta_r, wo + ko + 16u), z1 = ld4(noise_r, wo + ko + 16u);
             const f32x4 a0 = sgn ? w0 - z0 : w0 + z0, a1 = sgn ? w1 - z1 : w1 + z1;
-            acc = chain_chunk(acc, a0, a1, scr_r, row_lo, T, c);
-        }
-    }
-    return acc;
-}
-
-// The same chain with w and the bias start value read from a row staged in LDS (certify_queue: LDS_ROW floats, the
-// bias in the first pad word)
-__device__ __forceinline__ float chain_lds(const float* wrow, rsrc_t scr_r, uint32_t row_lo) {
-    float acc = wrow[128];
-#pragma unroll
-    for (int T = 0; T < 4; ++T) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const f32x4 a0 = *reinterpret_cast<const f32x4*>(wrow + 32 * T + 8 * c);
-            const f32x4 a1 = *reinterpret_cast<const f32x4*>(wrow + 32 * T + 8 * c + 4);
             acc = chain_chunk(acc, a0, a1, scr_r, row_lo, T, c);
         }
     }
@@ -1284,105 +1272,174 @@ struct ListItems {
     }
 };
 
-// Pass 2 of the certify, by the whole workgroup (every thread calls it, with or without items). The threads' items
-// (owner thread, vocabulary id) are numbered owner by owner with a wave scan and one cross-wave prefix through LDS and
-// written to a queue in LDS; the queue is worked off in batches of CERT_BATCH items and rounds of CERT_ROWS: the 32-lane
-// groups stage one candidate row per item (one ld4 of theta and one of the noise per lane, a full 512-byte line each;
-// fp32(W0 +/- delta) as logit_chain forms it, the bias start value in the row's pad), then thread j runs item j's
-// chain from its staged row (chain_lds; h from the owner's lane scratch) into the item's result slot. After a batch
-// each owner takes its results in item order. So the rounds of a step are its items over CERT_ROWS, whichever lanes
-// own them. each(f) calls f(id) for the thread's n_mine items in order; sink(L, id) receives them in the same order.
-// wscr_r: the lane scratch of the workgroup's eight waves. LDS (floats): the lists | 8 wave totals | queue | results |
-// rows. pm: DECODE_PROF slots of the step (CERT_PROF_AT(t) + 1; < 0: none): queue built, first round's rows staged,
-// chains done.
+// Pass 2 of the certify, wave by wave (every thread calls it, with or without items). A wave's items all belong to its
+// own 32 rows of h and its own sign, so the wave certifies them alone on the fp32 MFMA pipe the token phase leaves idle:
+// the lanes' items (owner lane, vocabulary id) are numbered owner by owner with a wave scan and written to the wave's
+// item list in LDS, which is worked off in batches of CERT_ITEMS and tiles of 32 consecutive items (the last tile padded
+// with the batch's last item). A tile's 32 candidate rows are staged into the wave's private tile as stage_store lays a
+// sign's tile out (fp32(W0 +/- delta) as logit_chain forms it, the biases as bias_init reads them) and multiplied with
+// the wave's B operand hB, still live from the logit loop: mfma_tile's chain, k block by k block. Lane (row r, half hh)
+// then holds the logits of row r for the tile's slots (a & 3) + 8 (a >> 2) + 4 hh and writes those whose item is owned
+// by row r over the item's word; after a batch each owner takes its results in item order. The staging is pipelined by
+// k block: the loads of block T + 2 (the next tile's from T = 2 on) are issued before block T's MFMAs, and a block's
+// columns of the tile are overwritten only after the previous tile's MFMAs of that block have read them. Nothing but
+// the wave's own LDS traffic has to be ordered inside the loops: one workgroup barrier in front (the stage buffers the
+// tiles lie over are read until then), none after it.
+// each(f) calls f(id) for the thread's n_mine items in order; sink(L, id) receives them in the same order.
+// LDS (floats): the lists | per wave: tile (SIGN_FLOATS) | 32 biases | CERT_ITEMS item / result words. pm: DECODE_PROF
+// slots of the step (CERT_PROF_AT(t) + 1; < 0: none), wave 0's: lists built, first tile staged, all tiles done.
 #define CERT_PROF_AT(t) (640 + 5 * ((t) + 1))   // + 0 scan done .. + 4 records fed (beyond the step marks of T <= 20)
-#define CERT_ROWS 192
-#define CERT_BATCH (8 * CERT_ROWS)
-#define CERT_TOT_AT (NTHREADS * SCREEN_HIT_CAP)
-#define CERT_QUEUE_AT (CERT_TOT_AT + 16)
-#define CERT_RES_AT (CERT_QUEUE_AT + CERT_BATCH)
-#define CERT_ROWS_AT (CERT_RES_AT + CERT_BATCH)
-static_assert(CERT_ROWS_AT % 4 == 0 && CERT_ROWS_AT + CERT_ROWS * LDS_ROW <= 2 * STAGE64_FLOATS, "certify LDS layout");
-#define CERT_ID_BITS 23                      // item = owner thread << 23 | id (bit 31: the owner's sign)
+#define CERT_PROF_WAVE_AT(t) (736 + 16 * (t))  // DECODE_PROF: + wave, the wave's item and distinct-id counts of step t >= 1
+#define CERT_ITEMS 320                      // 10 tiles
+#define CERT_WAVE_AT (NTHREADS * SCREEN_HIT_CAP)
+#define CERT_WAVE_FLOATS (SIGN_FLOATS + 32 + CERT_ITEMS)
+#define SCREEN_LDS_FLOATS (CERT_WAVE_AT + 8 * CERT_WAVE_FLOATS)     // the screened kernels' dynamic LDS
+static_assert(CERT_ITEMS % 32 == 0 && CERT_WAVE_AT % 4 == 0 && CERT_WAVE_FLOATS % 4 == 0, "certify LDS layout");
+// (a CU's 160 KB, less the 256 bytes of static LDS that __syncthreads_or brings into the screened kernels)
+static_assert(SCREEN_LDS_FLOATS >= 2 * STAGE64_FLOATS && SCREEN_LDS_FLOATS * 4 + 256 <= 160 * 1024, "certify LDS size");
+#define CERT_ID_BITS 23                      // item = owner lane << 23 | id
+#define CERT_ID_MASK ((1u << CERT_ID_BITS) - 1u)
+
+// orders the wave's own LDS stores before its later LDS loads in the compiler (the hardware runs a wave's LDS
+// instructions in order): no instruction
+__device__ __forceinline__ void wave_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// k block T of a tile's staging: lane l holds k 32 T + 4 (l & 7) .. + 3 of rows 8 u + (l >> 3)
+struct CertRegs {
+    f32x4 w[4], z[4];
+};
+// iw: the tile's 32 item words; the items at or past `nv` repeat item nv - 1
+__device__ __forceinline__ void cert_load(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, const uint32_t* iw, int nv,
+                                          int T, CertRegs& r) {
+    const int lane = lane_fresh();
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const uint32_t v = iw[min(8 * u + (lane >> 3), nv - 1)] & CERT_ID_MASK;
+        const uint32_t wo = 4u * ((uint32_t)p.off_log_w + 128u * v) + 16u * (uint32_t)(8 * T + (lane & 7));
+        r.w[u] = ld4(theta_r, wo);
+        r.z[u] = ld4(noise_r, wo);
+    }
+}
+__device__ __forceinline__ void cert_load_bias(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, const uint32_t* iw,
+                                               int nv, float& bw, float& bz) {
+    const uint32_t v = iw[min(lane_fresh() & 31, nv - 1)] & CERT_ID_MASK;
+    const uint32_t bo = 4u * ((uint32_t)p.off_log_b + v);
+    bw = ld1(theta_r, bo);
+    bz = ld1(noise_r, bo);
+}
+// the block into the columns stage_store gives it (k quad q = 8 T + (l & 7): T * 32 + (q & 1) * 16 + 4 * ((q & 7) >> 1))
+__device__ __forceinline__ void cert_store(float* tile, int sgn, int T, const CertRegs& r) {
+    const int lane = lane_fresh(), q = lane & 7;
+    float* b = tile + (lane >> 3) * LDS_ROW + T * 32 + (q & 1) * 16 + 4 * (q >> 1);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        *reinterpret_cast<f32x4*>(b + 8 * u * LDS_ROW) = sgn ? r.w[u] - r.z[u] : r.w[u] + r.z[u];
+}
+
 template <class Each, class Sink>
-__device__ __forceinline__ void certify_queue(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, rsrc_t wscr_r,
-                                              float* lds, int tid, int n_mine, const Each& each, Sink&& sink, int pm) {
-    uint32_t* lw = reinterpret_cast<uint32_t*>(lds);
-    float* rows = lds + CERT_ROWS_AT;
-    const int lane = tid & 63, wave = tid >> 6;
+__device__ __forceinline__ void certify_tiles(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, int sgn,
+                                              const float (&hB)[64], float* lds, int tid, int n_mine, const Each& each,
+                                              Sink&& sink, int pm) {
+    const int lane = tid & 63, hh = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float* tile = lds + CERT_WAVE_AT + wave * CERT_WAVE_FLOATS;
+    float* bias = tile + SIGN_FLOATS;
+    uint32_t* items = reinterpret_cast<uint32_t*>(bias + 32);
     int inc = n_mine;                                        // inclusive scan over the wave
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const int u = __shfl_up(inc, d);
         inc += lane >= d ? u : 0;
     }
-    if (lane == 63) lw[CERT_TOT_AT + wave] = (uint32_t)inc;
-    __syncthreads();
-    int first = inc - n_mine, total = 0;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-        const int c = (int)lw[CERT_TOT_AT + w];
-        first += w < wave ? c : 0;
-        total += c;
-    }
-    for (int b0 = 0; b0 < total; b0 += CERT_BATCH) {
-        const int nb = min(CERT_BATCH, total - b0);
-        const bool mine = first < b0 + nb && first + n_mine > b0;     // some of the thread's items are in this batch
+    const int total = __builtin_amdgcn_readlane(inc, 63), first = inc - n_mine;
+    __syncthreads();                                         // the logit loop's last reads of the stage buffers are done
+#if DECODE_PROF
+    if (pm >= 0 && total == 0 && lane == 0)
+        p.seq[(size_t)(blockIdx.x * gridDim.y + blockIdx.y) * 4096 + CERT_PROF_WAVE_AT((pm - 1 - 640) / 5 - 1) + wave] = 0;
+#endif
+    for (int b0 = 0; b0 < total; b0 += CERT_ITEMS) {
+        const int nb = min(CERT_ITEMS, total - b0);
+        const bool mine = first < b0 + nb && first + n_mine > b0;     // some of the lane's items are in this batch
         if (mine) {
             int pos = first - b0;
             each([&](int v) {
-                if ((unsigned)pos < (unsigned)nb) lw[CERT_QUEUE_AT + pos] = ((uint32_t)tid << CERT_ID_BITS) | (uint32_t)v;
+                if ((unsigned)pos < (unsigned)nb) items[pos] = ((uint32_t)lane << CERT_ID_BITS) | (uint32_t)v;
                 ++pos;
             });
         }
-        __syncthreads();
-        if (pm >= 0) PROF_MARK(pm + 0);
-        for (int r0 = 0; r0 < nb; r0 += CERT_ROWS) {
-            const int nr = min(CERT_ROWS, nb - r0);
-            const int q = tid & 31, g = tid >> 5;
-            for (int j0 = 0; j0 < nr; j0 += 64) {            // 16 groups x 4 rows in flight
-                f32x4 w[4], z[4];
-                float bw[4], bz[4];
-                uint32_t it[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    it[u] = lw[CERT_QUEUE_AT + r0 + min(j0 + g + 16 * u, nr - 1)];
-                    const uint32_t v = it[u] & ((1u << CERT_ID_BITS) - 1u);
-                    const uint32_t wo = 4u * ((uint32_t)p.off_log_w + 128u * v) + 16u * (uint32_t)q;
-                    const uint32_t bo = 4u * ((uint32_t)p.off_log_b + v);
-                    w[u] = ld4(theta_r, wo);
-                    z[u] = ld4(noise_r, wo);
-                    bw[u] = ld1(theta_r, bo);
-                    bz[u] = ld1(noise_r, bo);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int j = j0 + g + 16 * u;
-                    if (j < nr) {
-                        const bool sg = (it[u] >> 31) != 0;
-                        *reinterpret_cast<f32x4*>(rows + j * LDS_ROW + 4 * q) = sg ? w[u] - z[u] : w[u] + z[u];
-                        if (q == 0) rows[j * LDS_ROW + 128] = sg ? bw[u] - bz[u] : bw[u] + bz[u];
-                    }
-                }
+        wave_lds_order();
+#if DECODE_PROF
+        if (pm >= 0 && b0 == 0) {
+            // the wave's items and the distinct ids among its first batch's, for the step's table (scripts/ablate.py):
+            // seq slot CERT_PROF_WAVE_AT(t) + wave = items | distinct << 16
+            int dist = 0;
+            for (int j = lane; j < nb; j += 64) {
+                const uint32_t v = items[j] & CERT_ID_MASK;
+                bool seen = false;
+                for (int k = 0; k < j; ++k) seen = seen || (items[k] & CERT_ID_MASK) == v;
+                dist += seen ? 0 : 1;
             }
-            __syncthreads();
-            if (pm >= 0 && r0 == 0) PROF_MARK(pm + 1);
-            if (tid < nr) {
-                const uint32_t item = lw[CERT_QUEUE_AT + r0 + tid];
-                const uint32_t owner = item >> CERT_ID_BITS;
-                const uint32_t row_lo = (owner >> 6) * (uint32_t)(SCR_SLOTS * 64 * 4) + 4u * (owner & 31u);
-                lds[CERT_RES_AT + r0 + tid] = chain_lds(rows + tid * LDS_ROW, wscr_r, row_lo);
-            }
-            __syncthreads();
+#pragma unroll
+            for (int dd = 32; dd >= 1; dd >>= 1) dist += __shfl_xor(dist, dd);
+            if (lane == 0)
+                p.seq[(size_t)(blockIdx.x * gridDim.y + blockIdx.y) * 4096 + CERT_PROF_WAVE_AT((pm - 1 - 640) / 5 - 1) + wave] =
+                    min(total, 0xffff) | (dist << 16);
         }
+#endif
+        if (pm >= 0) PROF_MARK(pm + 0);
+        const int nt = (nb + 31) >> 5;
+        CertRegs r[2];
+        float bw, bz;
+        cert_load(p, theta_r, noise_r, items, nb, 0, r[0]);
+        cert_load_bias(p, theta_r, noise_r, items, nb, bw, bz);
+        cert_load(p, theta_r, noise_r, items, nb, 1, r[1]);
+        for (int i = 0; i < nt; ++i) {
+            const uint32_t* iw = items + 32 * i;
+            const int nv = nb - 32 * i;                      // the tile's items (32 or more: a full tile)
+            f32x16 acc;
+#pragma unroll
+            for (int T = 0; T < 4; ++T) {
+                cert_store(tile, sgn, T, r[T & 1]);
+                if (T == 0) bias[lane_fresh() & 31] = sgn ? bw - bz : bw + bz;
+                if (T < 2) {
+                    cert_load(p, theta_r, noise_r, iw, nv, T + 2, r[T & 1]);
+                } else if (i + 1 < nt) {
+                    cert_load(p, theta_r, noise_r, iw + 32, nv - 32, T - 2, r[T & 1]);
+                    if (T == 2) cert_load_bias(p, theta_r, noise_r, iw + 32, nv - 32, bw, bz);
+                }
+                wave_lds_order();
+                if (pm >= 0 && i == 0 && T == 3) PROF_MARK(pm + 1);
+                if (T == 0) acc = bias_init(bias, hh);
+                acc = mfma_tile_k(acc, tile + (lane_fresh() & 31) * LDS_ROW + hh * 16, hB, T);
+            }
+            // slot -> owner: the tile's item words, all read before the results go over them
+            u32x4 ow[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) ow[g] = *reinterpret_cast<const u32x4*>(iw + 8 * g + 4 * hh);
+            wave_lds_order();
+#pragma unroll
+            for (int a = 0; a < 16; ++a) {
+                const int slot = (a & 3) + 8 * (a >> 2) + 4 * hh;
+                const uint32_t word = ow[a >> 2][a & 3];
+                const float L = acc[a];                      // (a copy: bit_cast of a vector element reads element 0)
+                if (slot < nv && ((word >> CERT_ID_BITS) & 31u) == (uint32_t)(lane_fresh() & 31))
+                    items[32 * i + slot] = __builtin_bit_cast(uint32_t, L);
+            }
+        }
+        wave_lds_order();
         if (pm >= 0) PROF_MARK(pm + 2);
         if (mine) {
             int pos = first - b0;
             each([&](int v) {
-                if ((unsigned)pos < (unsigned)nb) sink(lds[CERT_RES_AT + pos], v);
+                if ((unsigned)pos < (unsigned)nb) sink(__builtin_bit_cast(float, items[pos]), v);
                 ++pos;
             });
         }
+        wave_lds_order();                                    // the next batch's items go over the results
     }
 }
 
@@ -1894,8 +1951,8 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_decode_img64_kernel(DecodePar
 // logit tile, loaded during the previous step's last cell stage (PREFETCH: that load is issued)
 // SAMPLE: the sampled decode (nets.py:210-231): the logit loop stores its logits and stage sums (SampleStage), then
 // sample_pick draws each row's token with its uniform p.sample_u (fused path only)
-// SCREEN (PAIRS, greedy only): the logit loop runs in bf16 and the candidates it leaves are certified by fp32 chains
-// (ScreenStage / screen_scan / certify_queue above); tokens are those of the fp32 loop
+// SCREEN (PAIRS, greedy only): the logit loop runs in bf16 and the candidates it leaves are certified on fp32
+// MFMA tiles (ScreenStage / screen_scan / certify_tiles above); tokens are those of the fp32 loop
 template <bool PAIRS, bool PREFETCH, bool SAMPLE = false, bool MUT = false, bool SCREEN = false>
 __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, float* lds, int t, Stage64Regs& s64,
                                           bool& pre, float (&hB)[64], bool& hpre, const MutRes* mr = nullptr,
@@ -2031,8 +2088,7 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
                     const ListItems items{reinterpret_cast<const uint32_t*>(lds) + ctid * SCREEN_HIT_CAP, ccnt, c.hh, p.V1};
                     int n_mine = 0;
                     items([&](int) { ++n_mine; });
-                    const rsrc_t wscr_r = make_rsrc(p.scratch + (size_t)c.wg * 8 * (SCR_SLOTS * 64), 8 * SCR_SLOTS * 64 * 4);
-                    certify_queue(p, c.theta_r, c.noise_r, wscr_r, lds, ctid, n_mine, items,
+                    certify_tiles(p, c.theta_r, c.noise_r, c.sgn, hB, lds, ctid, n_mine, items,
                                   [&](float L, int v) { record1(st, L, v); }, CERT_PROF_AT(t) + 1);
                 }
                 PROF_MARK(CERT_PROF_AT(t) + 4);
@@ -3210,6 +3266,7 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_decode_steps2_kernel(DecodePa
 namespace {
 const size_t LDS64 = (size_t)(2 * STAGE64_FLOATS) * sizeof(float);
 const size_t LDS32 = (size_t)(2 * STAGE_FLOATS) * sizeof(float);
+const size_t LDS_SCREEN = (size_t)SCREEN_LDS_FLOATS * sizeof(float);  // the screened kernels: + the certify's wave tiles
 const size_t LDS_CELL2 = LDS64 + (size_t)4 * 1024 * sizeof(float);   // + the G = 2 hand-over buffer
 }
 
@@ -3219,13 +3276,13 @@ extern "C" hipError_t nicnes_decode_init() {
 #if DECODE_PROF
         {(const void*)nicnes_decode_step_kernel<true>, LDS64},
         {(const void*)nicnes_decode_step_kernel<false>, LDS64},
-        {(const void*)nicnes_decode_step_screen_kernel, LDS64},
+        {(const void*)nicnes_decode_step_screen_kernel, LDS_SCREEN},
 #endif
         {(const void*)nicnes_decode_img64_kernel, LDS64},
         {(const void*)nicnes_decode_steps_kernel<true>, LDS64},
         {(const void*)nicnes_decode_steps_kernel<false>, LDS64},
         {(const void*)nicnes_decode_steps_kernel<false, true>, LDS64},
-        {(const void*)nicnes_decode_steps_screen_kernel, LDS64},
+        {(const void*)nicnes_decode_steps_screen_kernel, LDS_SCREEN},
         {(const void*)nicnes_decode_steps_mut_kernel<true>, LDS64},
         {(const void*)nicnes_decode_steps_mut_kernel<false>, LDS64},
         {(const void*)nicnes_decode_logit_kernel<4, true>, LDS64},
@@ -3347,7 +3404,7 @@ extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead*
 #if !DECODE_PROF
             if (!mut && pairs && sa && sa->cap && sa->norm) {
                 hipLaunchKernelGGL(nicnes_screen_norm_kernel, dim3(member_count), block, 0, stream, *p, *sa);
-                hipLaunchKernelGGL(nicnes_decode_steps_screen_kernel, grid, block, LDS64, stream, *p, *sa);
+                hipLaunchKernelGGL(nicnes_decode_steps_screen_kernel, grid, block, LDS_SCREEN, stream, *p, *sa);
             } else if (mut && pairs)
                 hipLaunchKernelGGL(nicnes_decode_steps_mut_kernel<true>, grid, block, LDS64, stream, *p, *mh);
             else if (mut)
@@ -3362,7 +3419,7 @@ extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead*
             if (scr) hipLaunchKernelGGL(nicnes_screen_norm_kernel, dim3(member_count), block, 0, stream, *p, *sa);
             for (int t = -1; t <= p->T; ++t) {
                 if (scr)
-                    hipLaunchKernelGGL(nicnes_decode_step_screen_kernel, grid, block, LDS64, stream, *p, *sa, t);
+                    hipLaunchKernelGGL(nicnes_decode_step_screen_kernel, grid, block, LDS_SCREEN, stream, *p, *sa, t);
                 else if (pairs)
                     hipLaunchKernelGGL(nicnes_decode_step_kernel<true>, grid, block, LDS64, stream, *p, t);
                 else
@@ -3506,40 +3563,44 @@ extern "C" hipError_t nicnes_launch_test_logit_chain(const DecodeParams* p, uint
     return hipGetLastError();
 }
 
-// ========== test entry: given (row, id) items through the screened decode's certify_queue ======================
+// ========== test entry: given (row, id) items through the screened decode's certify_tiles ======================
 // One workgroup of the decode's shape. hin [128, 128] is laid out as its eight waves' lane scratch (wave w: sign w >> 2,
-// rows 32 (w & 3) .. + 31, both signs the same rows); the items, grouped by row (row_start [129], ids and their
-// positions in the caller's list), are owned by the thread the decode gives that row of sign sgn, and each item's
-// logit lands at its position in out.
+// rows 32 (w & 3) .. + 31, both signs the same rows), from where the waves of sign sgn load their B operand as step_body
+// does. The items come grouped by owner (lane_start [257], group 2 row + half; ids and their positions in the caller's
+// list): group (row, half) is owned by lane row % 32 + 32 half of the row's wave of sign sgn, and each item's logit lands
+// at its position in out.
 __global__ __launch_bounds__(NTHREADS) void nicnes_test_certify_kernel(DecodeParams p, uint64_t nidx, int sgn,
-                                                                       const int32_t* row_start, const int32_t* ids,
+                                                                       const int32_t* lane_start, const int32_t* ids,
                                                                        const int32_t* pos_of, float* out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const rsrc_t theta_r = make_rsrc(p.theta, 4u * (uint32_t)p.D);
     const rsrc_t noise_r = make_rsrc(p.noise + nidx, 4u * (uint32_t)p.D);
-    const rsrc_t wscr_r = make_rsrc(p.scratch, 8 * SCR_SLOTS * 64 * 4);
-    const bool owner = (wave >> 2) == sgn && lane < 32;
-    const int row = 32 * (wave & 3) + (lane & 31);
-    const int i0 = owner ? row_start[row] : 0, i1 = owner ? row_start[row + 1] : 0;
+    const rsrc_t scr_r = make_rsrc(p.scratch + (size_t)wave * SCR_SLOTS * 64, SCR_SLOTS * 64 * 4);
+    const bool owner = (wave >> 2) == sgn;
+    const int grp = 2 * (32 * (wave & 3) + (lane & 31)) + (lane >> 5);
+    const int i0 = owner ? lane_start[grp] : 0, i1 = owner ? lane_start[grp + 1] : 0;
+    float hB[64];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) hB[i] = ld1(scr_r, 4u * (uint32_t)lane, H_SLOT(i));
     auto each = [&](auto&& f) {
         for (int i = i0; i < i1; ++i) f(ids[i]);
     };
     int k = i0;
-    certify_queue(p, theta_r, noise_r, wscr_r, lds, tid, i1 - i0, each, [&](float L, int) { out[pos_of[k++]] = L; }, -1);
+    certify_tiles(p, theta_r, noise_r, sgn, hB, lds, tid, i1 - i0, each, [&](float L, int) { out[pos_of[k++]] = L; }, -1);
 }
 
 extern "C" hipError_t nicnes_launch_test_certify_items(const DecodeParams* p, uint64_t nidx, int sgn, const float* hin,
-                                                       const int32_t* row_start, const int32_t* ids,
+                                                       const int32_t* lane_start, const int32_t* ids,
                                                        const int32_t* pos_of, float* out, hipStream_t stream) {
     hipError_t e = hipFuncSetAttribute((const void*)nicnes_test_certify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)LDS64);
+                                       (int)LDS_SCREEN);
     if (e != hipSuccess) return e;
     for (int w = 0; w < 8; ++w)
         hipLaunchKernelGGL(nicnes_test_h_scratch_kernel, dim3(1), dim3(64), 0, stream, hin + (size_t)(w & 3) * 32 * 128,
                            p->scratch + (size_t)w * SCR_SLOTS * 64);
-    hipLaunchKernelGGL(nicnes_test_certify_kernel, dim3(1), dim3(NTHREADS), LDS64, stream, *p, nidx, sgn, row_start, ids,
-                       pos_of, out);
+    hipLaunchKernelGGL(nicnes_test_certify_kernel, dim3(1), dim3(NTHREADS), LDS_SCREEN, stream, *p, nidx, sgn, lane_start,
+                       ids, pos_of, out);
     return hipGetLastError();
 }
 

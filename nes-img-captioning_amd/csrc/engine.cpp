@@ -1858,7 +1858,14 @@ int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member
 
 int nicnes_test_certify_items(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
                               const float* h_rows, const int32_t* items_host, int32_t n_items, float* out, void* stream) {
-    if (!h || !h_rows || n_items < 0 || (n_items && (!items_host || !out)) || member < 0 || (sign != 0 && sign != 1))
+    return nicnes_test_certify_items_owned(h, iteration, member, sigma, sign, 0, h_rows, items_host, n_items, out, stream);
+}
+
+int nicnes_test_certify_items_owned(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
+                                    int32_t owner_by_id, const float* h_rows, const int32_t* items_host, int32_t n_items,
+                                    float* out, void* stream) {
+    if (!h || !h_rows || n_items < 0 || (n_items && (!items_host || !out)) || member < 0 || (sign != 0 && sign != 1) ||
+        (owner_by_id != 0 && owner_by_id != 1))
         return NICNES_ERR_INVALID;
     if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
@@ -1880,16 +1887,24 @@ int nicnes_test_certify_items(nicnes_handle* h, uint64_t iteration, int32_t memb
         h->sc_sigma = sigma;
         h->sc_valid = true;
     }
-    // the items grouped by row, in the caller's order inside a row: row_start [129] | ids [n] | positions [n]
-    std::vector<int32_t> host(129 + 2 * (size_t)n_items, 0);
-    int32_t* row_start = host.data();
-    int32_t* ids = row_start + 129;
+    // the items grouped by owner lane (group 2 row + half; half 0, or the id's bit 2 as the decode's lists have it):
+    // lane_start [257] | ids [n] | positions [n]. Inside a group the caller's order, or increasing ids (by id: the order
+    // a decode's lane meets them in; repeats keep the caller's order)
+    std::vector<int32_t> host(257 + 2 * (size_t)n_items, 0);
+    int32_t* lane_start = host.data();
+    int32_t* ids = lane_start + 257;
     int32_t* pos_of = ids + n_items;
-    for (int32_t i = 0; i < n_items; ++i) ++row_start[items_host[2 * i] + 1];
-    for (int r = 0; r < 128; ++r) row_start[r + 1] += row_start[r];
-    std::vector<int32_t> fill(row_start, row_start + 128);
-    for (int32_t i = 0; i < n_items; ++i) {
-        const int32_t at = fill[items_host[2 * i]]++;
+    auto group = [&](int32_t i) { return 2 * items_host[2 * i] + (owner_by_id ? (items_host[2 * i + 1] >> 2) & 1 : 0); };
+    std::vector<int32_t> order((size_t)n_items);
+    for (int32_t i = 0; i < n_items; ++i) order[i] = i;
+    if (owner_by_id)
+        std::stable_sort(order.begin(), order.end(),
+                         [&](int32_t a, int32_t b) { return items_host[2 * a + 1] < items_host[2 * b + 1]; });
+    for (int32_t i = 0; i < n_items; ++i) ++lane_start[group(i) + 1];
+    for (int g = 0; g < 256; ++g) lane_start[g + 1] += lane_start[g];
+    std::vector<int32_t> fill(lane_start, lane_start + 256);
+    for (int32_t i : order) {
+        const int32_t at = fill[group(i)]++;
         ids[at] = items_host[2 * i + 1];
         pos_of[at] = i;
     }
@@ -1906,7 +1921,7 @@ int nicnes_test_certify_items(nicnes_handle* h, uint64_t iteration, int32_t memb
     p.scratch = h->dscratch;        // eight waves' lane scratch hold the rows of h (no decode runs beside this)
     const uint64_t nidx = nn_noise_index(h->cfg.noise_seed, iteration, (uint64_t)member, h->cfg.noise_len, (uint64_t)h->D);
     if (e == hipSuccess)
-        e = nicnes_launch_test_certify_items(&p, nidx, sign, h_rows, dev, dev + 129, dev + 129 + n_items, out, s);
+        e = nicnes_launch_test_certify_items(&p, nidx, sign, h_rows, dev, dev + 257, dev + 257 + n_items, out, s);
     const hipError_t e2 = hipStreamSynchronize(s);    // host and dev live until the kernel has read them
     (void)hipFree(dev);
     HIPC(h, e);

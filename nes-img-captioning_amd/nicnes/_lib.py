@@ -24,7 +24,7 @@ EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_create', 'nicne
            'nicnes_set_decode_coop', 'nicnes_decode_path', 'nicnes_sum_sensitivity', 'nicnes_grad_partial_range',
            'nicnes_evaluate_theta', 'nicnes_set_sample_draws', 'nicnes_set_rows_per_image',
            'nicnes_last_decode_lse', 'nicnes_test_logit_chain', 'nicnes_test_score_rows',
-           'nicnes_test_certify_items',
+           'nicnes_test_certify_items', 'nicnes_test_certify_items_owned',
            'nicnes_set_decode_screen', 'nicnes_screen_stats', 'nicnes_split_create', 'nicnes_split_destroy',
            'nicnes_split_decode', 'nicnes_split_score', 'nicnes_split_evaluate']
 
@@ -105,6 +105,7 @@ def lib(path=None):
         'nicnes_screen_stats': (c.c_int, [vp, vp]),
         'nicnes_test_logit_chain': (c.c_int, [vp, u64, i32, f32, i32, vp, vp, vp, vp]),
         'nicnes_test_certify_items': (c.c_int, [vp, u64, i32, f32, i32, vp, vp, i32, vp, vp]),
+        'nicnes_test_certify_items_owned': (c.c_int, [vp, u64, i32, f32, i32, i32, vp, vp, i32, vp, vp]),
         'nicnes_test_score_rows': (c.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
         'nicnes_sum_sensitivity': (c.c_int, [vp, i32, f32, vp, vp]),
         'nicnes_split_create': (c.c_int, [vp, vp, i32, vp, i32, vp, vp, vp, i64, f64, c.POINTER(vp), vp]),

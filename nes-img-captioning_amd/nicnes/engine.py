@@ -436,18 +436,20 @@ class Engine:
             torch.cuda.current_stream().synchronize()   # hr stays alive until the kernel has read it
         return om, oc
 
-    def test_certify_items(self, iteration, member, sigma, sign, h_rows, items):
+    def test_certify_items(self, iteration, member, sigma, sign, h_rows, items, owner_by_id=False):
         """Test entry: items [n, 2] of (row < 128, vocabulary id) over h_rows [128, 128] through the screened decode's
-        cooperative certify; an fp32 tensor [n] of their exact logits. An id or row out of range raises."""
+        tile certify; an fp32 tensor [n] of their exact logits. An id or row out of range raises. owner_by_id: an item
+        belongs to the lane half its id's bit 2 names, as in a decode (default: to lane half 0 of its row)."""
         hr = torch.as_tensor(h_rows, dtype=torch.float32, device=self.device).contiguous()
         assert hr.shape == (128, self.cfg.rnn_size)
         it = np.ascontiguousarray(np.asarray(items, dtype=np.int32).reshape(-1, 2))
         n = int(it.shape[0])
         out = torch.empty((max(n, 1),), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            check(self.L.nicnes_test_certify_items(self.h, ctypes.c_uint64(iteration), int(member), ctypes.c_float(sigma),
-                                                   int(sign), _ptr(hr), it.ctypes.data_as(ctypes.c_void_p), n, _ptr(out),
-                                                   self._stream()), self.h, 'test_certify_items')
+            check(self.L.nicnes_test_certify_items_owned(self.h, ctypes.c_uint64(iteration), int(member),
+                                                         ctypes.c_float(sigma), int(sign), int(bool(owner_by_id)), _ptr(hr),
+                                                         it.ctypes.data_as(ctypes.c_void_p), n, _ptr(out),
+                                                         self._stream()), self.h, 'test_certify_items')
         return out[:n]
 
     def test_score_rows(self, seq, member_batch=None, lp=None, base=None):

@@ -74,14 +74,16 @@ def cell_stages(k, seq):
 
 def certify_phases(k, seq):
     """DECODE_PROF=1 build, screened step launches: the certify of step t split at the marks CERT_PROF_AT(t) =
-    640 + 5 (t + 1) + {0: scan done, 1: queue built, 2: first round's rows staged, 3: chains done, 4: records fed}
-    (thread 0's clock; 1-3 only in a workgroup step with items), from the end of the logit loop (120 + 24 (t + 1)):
-    mean / median / max over workgroups, us."""
+    640 + 5 (t + 1) + {0: scan done, 1: lists built, 2: first tile staged, 3: all tiles done, 4: records fed}
+    (thread 0's clock, so wave 0's tiles; 1-3 only in a workgroup step where wave 0 has items), from the end of the
+    logit loop (120 + 24 (t + 1)): mean / median / max over workgroups, us. Then, from the words the waves leave at
+    CERT_PROF_WAVE_AT(t) = 736 + 16 t + wave (items | distinct ids of the first batch << 16): tiles per wave (mean, max
+    over waves; the slowest wave of a workgroup, mean over workgroups) and distinct ids against items per wave."""
     raw = seq.reshape(-1, 4096).cpu().numpy().astype(np.int64) & 0xffffffff
     ts = raw[:, :1024]
     if not ts[:, 640 + 5 * 2].any():
         return                                                # not the screened kernel
-    print(k, 'certify t: wgs_with_items | scan | queue | first_rows | chains(all rounds) | records | whole  '
+    print(k, 'certify t: wgs_with_items | scan | lists | first_tile | all tiles (wave 0) | records | whole  '
           '(mean/median/max us over workgroups)')
     for t in range(1, 17):
         c = 640 + 5 * (t + 1)
@@ -96,6 +98,16 @@ def certify_phases(k, seq):
             k, t, int(has.sum()), f(d(ts[:, c], b)), f(d(ts[has, c + 1], ts[has, c])),
             f(d(ts[has, c + 2], ts[has, c + 1])), f(d(ts[has, c + 3], ts[has, c + 2])),
             f(d(ts[has, c + 4], ts[has, c + 3])), f(d(ts[:, c + 4], b))))
+    print(k, 'certify t: items per wave mean/max | tiles per wave mean/max | slowest wave of a workgroup, tiles, mean | '
+          'distinct ids / items of the waves\' first batches')
+    for t in range(1, 17):
+        w = ts[:, 736 + 16 * t: 736 + 16 * t + 8]
+        items, dist = w & 0xffff, w >> 16
+        tiles = (items + 31) // 32
+        first = np.minimum(items, 320)
+        print('%s t=%-2d %.1f/%d | %.2f/%d | %.2f | %d / %d = %.3f' % (
+            k, t, items.mean(), items.max(), tiles.mean(), tiles.max(), tiles.max(axis=1).mean(), dist.sum(), first.sum(),
+            dist.sum() / max(first.sum(), 1)))
 
 
 def split_spans(k, seq, S=4):
