@@ -423,6 +423,65 @@ int nicnes_test_score_rows(nicnes_handle* h, const int32_t* seq_dev, int32_t n_c
                            const int32_t* member_batch_host, const float* lp_dev, const double* base_dev,
                            double* scores_out_dev, double* fitness_out_dev, void* stream);
 
+/* ---- nic_es: the truncation-selection GA (src/algorithm/nic_es/) ----------------------------------------------------
+ * The reference keeps every parent, offspring and elite as a .pth file on a shared disk (11.46 MB each). Here a parent
+ * is a row of a device table and an offspring is (parent slot, noise index, sign): pair k of a generation perturbs
+ * parent parent_of[k] by delta'_k, taken from the shared noise table at the existing index rule on (generation, k),
+ * and its two offspring, ids 2k (parent + delta') and 2k + 1 (parent - delta'), share one staging of that row. Only
+ * the selected offspring are ever written out, by nicnes_es_advance, on the device.
+ * nicnes_es_create allocates the state on the handle (synchronising): two parent tables [max_parents, Dp] fp32
+ * (double-buffered: the selected offspring reference the old parents), an elite table [max_elites, Dp], Dp = D rounded
+ * up to 64 floats. Replaces the directories of ESIteration (src/algorithm/nic_es/iterations.py). */
+int nicnes_es_create(nicnes_handle* h, int32_t max_parents, int32_t max_elites);
+int nicnes_es_free(nicnes_handle* h);
+/* ES mutation (PolicyNet.evolve with the parent as param_vector, src/algorithm/nets.py:96-113): NICNES_MUTATION_PLAIN,
+ * or NICNES_MUTATION_SCALE = SM-PROPORTIONAL, delta'[j] = fp32(fp32(sigma z[j]) * a[j]) with a[j] = |theta_p[j]|, or
+ * mean|theta_p| where theta_p[j] is exactly 0; the mean is the engine's (fp32 of an fp64 sum in a fixed order, formed
+ * when the row is written). SM-G-SUM / SM-VECTOR: NICNES_ERR_UNSUPPORTED. Independent of nicnes_set_mutation. */
+int nicnes_es_set_mutation(nicnes_handle* h, int32_t mode);
+/* Parent row `slot` of the current table <- theta32 [D] fp32 (device), and its statistics; the parent count is set
+ * apart (slots [0, count) are the parents an evaluate may name). Replaces ESIteration.init_parents / the parent paths
+ * of ESTask (nic_es_master.py:27-34). */
+int nicnes_es_set_parent(nicnes_handle* h, int32_t slot, const float* theta32, void* stream);
+int nicnes_es_set_parent_count(nicnes_handle* h, int32_t count);
+/* A row back: table 0 = the current parents, 1 = the elites; theta32_out [D] fp32 (device). */
+int nicnes_es_get_row(nicnes_handle* h, int32_t table, int32_t slot, float* theta32_out, void* stream);
+/* The row's statistics as the mutation uses them (synchronising): fp32 mean|theta| and the count of exact zeros. */
+int nicnes_es_row_stats(nicnes_handle* h, int32_t table, int32_t slot, float* mean_abs_out_host,
+                        int64_t* zeros_out_host, void* stream);
+/* Evaluate pairs [pair_begin, pair_begin + count) of `generation`: replaces ESWorker.fitness
+ * (src/algorithm/nic_es/nic_es_worker.py) for a slice of the offspring. parent_of_host [count] (HOST, copied): the
+ * parent slot of each pair of the slice; member_batch_host as in nicnes_evaluate_batches (nullable); fitness_out
+ * [count, 2] fp64 = the fitness of offspring (2k, 2k + 1); seq_out [count, 2, B, seq_length] int32 and logprob_out
+ * likewise fp32, both nullable. Always the fused decode (128-row slabs, one workgroup per pair and slab): a shape forced
+ * by nicnes_set_decode_split other than (1, 4), and the sampled fitness modes, are NICNES_ERR_UNSUPPORTED. Screening
+ * follows nicnes_set_decode_screen as in nicnes_evaluate. Only enqueues. */
+int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin, int32_t count, float sigma,
+                       const int32_t* parent_of_host, const int32_t* member_batch_host, double* fitness_out,
+                       int32_t* seq_out, float* logprob_out, void* stream);
+/* One offspring's parameters, fp32(theta_parent +- delta') exactly as the decode forms them: theta32_out [D] fp32
+ * (device). sign 0: +, 1: -. What ESWorker writes to its offspring .pth (for tests, the wire and snapshots). */
+int nicnes_es_offspring(nicnes_handle* h, uint64_t generation, int32_t pair, int32_t sign, float sigma, int32_t parent,
+                        float* theta32_out, void* stream);
+/* Truncation selection (the sort of ESMaster.run_master, nic_es_master.py): fitness [n] fp64 (device; a generation's
+ * [pairs, 2] ravelled, n <= 2 max_members) -> order_out [n_keep] int32 (device) = the offspring ids in descending
+ * fitness, ties to the lower id, NaN last, -0 equal to +0. n_keep outside [1, n]: NICNES_ERR_INVALID. Only enqueues. */
+int nicnes_es_select(nicnes_handle* h, const double* fitness, int32_t n, int32_t n_keep, int32_t* order_out,
+                     void* stream);
+/* The next generation's parents (ESIteration.record_parents): the other table's rows [0, n_front) <- elite rows
+ * [0, n_front), rows n_front + i <- offspring order[i] of `generation` (order [n_keep] int32, device, as
+ * nicnes_es_select wrote it; parent_of_host [n_pairs] the parent slots of ALL pairs of the generation, so every rank
+ * holding the gathered fitness advances identically whatever shard it evaluated). The rows' statistics are refreshed,
+ * the tables swap and the parent count becomes n_front + n_keep. Only enqueues. */
+int nicnes_es_advance(nicnes_handle* h, uint64_t generation, float sigma, const int32_t* parent_of_host, int32_t n_pairs,
+                      const int32_t* order, int32_t n_keep, int32_t n_front, void* stream);
+/* Elite row elite_slot <- row `slot` of `table` (0: the current parents, a new elite, Podium.record_elites' copy of the
+ * .pth; 1: the elites, an elite moving down the podium) with its statistics. */
+int nicnes_es_set_elite(nicnes_handle* h, int32_t elite_slot, int32_t table, int32_t slot, void* stream);
+/* The handle's theta <- a row (table 0 parents, 1 elites), a device copy, so that nicnes_split_evaluate /
+ * nicnes_evaluate_theta validate an elite candidate (ESMaster's accuracy_on of the elite .pth). */
+int nicnes_es_load_theta(nicnes_handle* h, int32_t table, int32_t slot, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,14 @@ struct MutHead {
     int32_t mode;
 };
 
+// nic_es (the *_es kernels' second argument; DecodeParams and every other kernel stay as they are): member k of the
+// launch perturbs its own base theta, row parent_of[k] of the parent table, instead of DecodeParams::theta
+struct ParentArgs {
+    const float* parents;        // fp32 [max_parents, stride]
+    const int32_t* parent_of;    // [members] parent slot of each member of the launch
+    int64_t stride;              // Dp: D rounded up to 64 floats
+};
+
 // launch kinds recorded next to the timing events
 #define DK_IMG 0
 #define DK_STEP 1        // fused step kernel (logits of t + cell of t + 1)
@@ -94,7 +102,12 @@ extern "C" hipError_t nicnes_decode_init();
 extern "C" hipError_t nicnes_decode_occupancy(int* coop_per_cu, int* sample_per_cu);
 // shifts the per-member and per-workgroup pointers of *p to member m0 (a decode of members m0.. on
 // its own stream; nslabs = the launch's row slabs)
-extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead* mh, ScreenArgs* sa = nullptr);
+extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead* mh, ScreenArgs* sa = nullptr,
+                                    ParentArgs* pa = nullptr);
+// nic_es: the fused greedy decode (G = 4, S = 1, no sampling, no decode-formed delta') of members with their own base
+// theta (ParentArgs); screened when sa has its buffers and the decode is greedy-only with the bounded lse
+extern "C" hipError_t nicnes_launch_decode_es(const DecodeParams* p, const ParentArgs* pa, int member_count, int nslabs,
+                                              hipStream_t stream, const ScreenArgs* sa = nullptr);
 // mh: nullable (or mode 0): no decode-formed delta'
 extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead* mh, int member_count, int nslabs,
                                            hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch,

@@ -1448,49 +1448,15 @@ __device__ __forceinline__ void certify_tiles(const DecodeParams& p, rsrc_t thet
 // NaN, which sticks: eps is then not finite and every step of the member runs the fp32 loop.
 __global__ __launch_bounds__(NTHREADS) void nicnes_screen_norm_kernel(DecodeParams p, ScreenArgs sa) {
     __shared__ float red[4][8];
-    const int tid = threadIdx.x, q = tid & 31, member = blockIdx.x;
-    const uint64_t nidx = p.noise_idx[member];
-    const rsrc_t w_r = make_rsrc(p.theta + p.off_log_w, 4u * 128u * (uint32_t)p.V1);
-    const rsrc_t z_r = make_rsrc(p.noise + nidx + p.off_log_w, 4u * 128u * (uint32_t)p.V1);
-    const rsrc_t b_r = make_rsrc(p.theta + p.off_log_b, 4u * (uint32_t)p.V1);
-    const rsrc_t bz_r = make_rsrc(p.noise + nidx + p.off_log_b, 4u * (uint32_t)p.V1);
-    float m[4] = {0.f, 0.f, 0.f, 0.f};
-    auto upd = [](float& mx, float x) { mx = (x > mx || x != x) ? x : mx; };
-    for (int v = tid >> 5; v < p.V1; v += NTHREADS / 32) {
-        const uint32_t off = 4u * (uint32_t)(128 * v + 4 * q);
-        const f32x4 w = ld4(w_r, off), z = ld4(z_r, off);
-        const f32x4 a = w + z, b = w - z;
-        float ssp = 0.f, ssm = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            ssp += a[e] * a[e];
-            ssm += b[e] * b[e];
-        }
-#pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) {
-            ssp += __shfl_xor(ssp, d);
-            ssm += __shfl_xor(ssm, d);
-        }
-        upd(m[0], ssp);
-        upd(m[1], ssm);
-    }
-    for (int v = tid; v < p.V1; v += NTHREADS) {
-        const float bw = ld1(b_r, 4u * (uint32_t)v), bz = ld1(bz_r, 4u * (uint32_t)v);
-        upd(m[2], fabsf(bw + bz));
-        upd(m[3], fabsf(bw - bz));
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) upd(m[i], __shfl_xor(m[i], d));
-        if ((tid & 63) == 0) red[i][tid >> 6] = m[i];
-    }
-    __syncthreads();
-    if (tid < 4) {
-        float r = red[tid][0];
-        for (int w = 1; w < 8; ++w) upd(r, red[tid][w]);
-        sa.norm[4 * member + tid] = r;
-    }
+#include "screen_norm_body.inc"
+}
+
+// nic_es: the norms of a member of its own parent row (ParentArgs; the member is blockIdx.x)
+__global__ __launch_bounds__(NTHREADS) void nicnes_screen_norm_es_kernel(DecodeParams p0, ParentArgs pa, ScreenArgs sa) {
+    __shared__ float red[4][8];
+    DecodeParams p = p0;
+    p.theta = pa.parents + (int64_t)pa.parent_of[blockIdx.x] * pa.stride;
+#include "screen_norm_body.inc"
 }
 
 // Measured and not kept (git history, r04): per-wave LDS progress words in place of the per-stage barrier (+0.4 %),
@@ -1844,95 +1810,7 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_decode_img_mut_kernel(DecodeP
 // nicnes_decode_img_kernel: identical x, written to X_SLOT.
 __global__ __launch_bounds__(NTHREADS) void nicnes_decode_img64_kernel(DecodeParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const Ctx c = make_ctx(p);
-    PROF_MARK(80);
-    const float* fcm = p.fc + (p.member_batch ? (size_t)p.member_batch[c.member] * p.B_img * p.F : 0);
-    const rsrc_t fc_r = make_rsrc(fcm, 4u * (uint32_t)p.B_img * (uint32_t)p.F);
-    const int fr = c.row_valid ? (c.b + c.sgn * p.sign_off) / p.rpi : 0;      // the lane's fc row (its image)
-    const int nK = p.F >> 7;
-    const uint32_t F = (uint32_t)p.F;
-    auto load = [&](int j, Stage64Regs& r) __attribute__((always_inline)) {
-        const int tid = c.wave * 64 + lane_fresh();
-        // thread tid: img_w row 64 (j & 1) + (tid >> 5) + 16 u, k 128 (j >> 1) + 4 (tid & 31) (stage64_store's rows)
-        const uint32_t vo = 4u * ((uint32_t)(tid >> 5) * F + 4u * (uint32_t)(tid & 31));
-        const uint32_t base = 4u * ((uint32_t)p.off_img_w + (uint32_t)(64 * (j & 1)) * F + 128u * (uint32_t)(j >> 1));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            r.w[u] = ld4(c.theta_r, vo, base + 64u * F * (uint32_t)u);
-            r.z[u] = ld4(c.noise_r, vo, base + 64u * F * (uint32_t)u);
-        }
-        const uint32_t bo = 4u * ((uint32_t)p.off_img_b + (uint32_t)(64 * (j & 1) + (tid & 63)));
-        r.bw = ld1(c.theta_r, bo);
-        r.bz = ld1(c.noise_r, bo);
-    };
-    auto load_fc = [&](int kc, float (&dst)[64]) __attribute__((always_inline)) {
-        const uint32_t frow = 4u * ((uint32_t)fr * F + 128u * (uint32_t)kc + 4u * (uint32_t)c.hh);
-#pragma unroll
-        for (int T = 0; T < 4; ++T)
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const f32x4 v = ld4(fc_r, frow + 4u * (uint32_t)(32 * T + 8 * a));
-#pragma unroll
-                for (int e = 0; e < 4; ++e) dst[16 * T + 4 * a + e] = v[e];
-            }
-    };
-    // two chains (unit blocks u0, u0 + 1) over one stage, accumulating (bias first at chunk 0)
-    auto mm = [&](const float* buf, bool first, const float (&Bop)[64], f32x16& A0, f32x16& A1)
-        __attribute__((always_inline)) {
-        const int lane = lane_fresh(), hh = lane >> 5;
-        const float* wsg = buf + c.sgn * (64 * LDS_ROW);
-        const float* bsg = buf + 2 * 64 * LDS_ROW + 64 * c.sgn;
-        if (first) {
-            A0 = bias_init(bsg, hh);
-            A1 = bias_init(bsg + 32, hh);
-        }
-        const float* row0 = wsg + (lane & 31) * LDS_ROW + 16 * hh;
-        const float* row1 = row0 + 32 * LDS_ROW;
-#pragma unroll
-        for (int T = 0; T < 4; ++T) {
-            f32x4 a0[4], a1[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                a0[q] = *reinterpret_cast<const f32x4*>(row0 + T * 32 + 4 * q);
-                a1[q] = *reinterpret_cast<const f32x4*>(row1 + T * 32 + 4 * q);
-            }
-#pragma unroll
-            for (int jj = 0; jj < 16; ++jj) {
-                A0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[jj >> 2][jj & 3], Bop[16 * T + jj], A0, 0, 0, 0);
-                A1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[jj >> 2][jj & 3], Bop[16 * T + jj], A1, 0, 0, 0);
-            }
-        }
-    };
-    const int tid0 = c.wave * 64;
-    Stage64Regs s64;
-    f32x16 acc[4];
-    float fcB[64], fcN[64];
-    load(0, s64);
-    load_fc(0, fcB);
-    stage64_store(lds, 64, tid0 + lane_fresh(), s64);
-    __syncthreads();
-#pragma unroll 1
-    for (int kc = 0; kc < nK; ++kc) {
-        load(2 * kc + 1, s64);                                   // stage 2 kc + 1: unit blocks 2-3
-        if (kc + 1 < nK) load_fc(kc + 1, fcN);
-        mm(lds, kc == 0, fcB, acc[0], acc[1]);
-        stage64_store(lds + STAGE64_FLOATS, 64, tid0 + lane_fresh(), s64);
-        __syncthreads();
-        if (kc + 1 < nK) load(2 * kc + 2, s64);                  // stage 2 kc + 2: unit blocks 0-1
-        mm(lds + STAGE64_FLOATS, kc == 0, fcB, acc[2], acc[3]);
-        if (kc + 1 < nK) stage64_store(lds, 64, tid0 + lane_fresh(), s64);
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 64; ++i) fcB[i] = fcN[i];
-    }
-    const uint32_t lo = 4u * (uint32_t)lane_fresh();
-#pragma unroll
-    for (int U = 0; U < 4; ++U)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st1(c.scr_r, lo, X_SLOT(16 * U + r), acc[U][r]);
-    st1(c.scr_r, lo, U_SLOT, 1.0f);
-    if (c.tid == 0) p.alive[c.wg] = 1;
-    PROF_MARK(81);
+#include "decode_img64_body.inc"
 }
 
 // ========== step kernel: logits + greedy token of step t, then the LSTM cell of step t+1 ========
@@ -2421,6 +2299,47 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_decode_steps_mut_kernel(Decod
     float hB[64];
     for (int t = -1; t <= p.T; ++t)
         if (!step_body<PAIRS, true, false, true>(p, c, lds, t, s64, pre, hB, hpre, &mr)) break;
+}
+
+// ========== nic_es: a base theta per member (ParentArgs) =========================================
+// The fused G = 4, S = 1 kernels with the workgroup's base set from the parent table: p.theta is read only where a
+// workgroup builds its buffer descriptors (make_ctx, StageSrc, the certify's descriptors, the norm kernel's), so a
+// by-value copy of DecodeParams with theta = the member's parent row runs the bodies above unchanged. The member of
+// a workgroup is blockIdx.x in each of these grids.
+__device__ __forceinline__ DecodeParams es_params(const DecodeParams& p, const ParentArgs& pa) {
+    DecodeParams q = p;
+    q.theta = pa.parents + (int64_t)pa.parent_of[blockIdx.x] * pa.stride;
+    return q;
+}
+
+__global__ __launch_bounds__(NTHREADS) void nicnes_decode_img64_es_kernel(DecodeParams p0, ParentArgs pa) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const DecodeParams p = es_params(p0, pa);
+#include "decode_img64_body.inc"
+}
+
+template <bool PAIRS>
+__global__ __launch_bounds__(NTHREADS) void nicnes_decode_steps_es_kernel(DecodeParams p0, ParentArgs pa) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const DecodeParams p = es_params(p0, pa);
+    const Ctx c = make_ctx(p);
+    Stage64Regs s64;
+    bool pre = false, hpre = false;
+    float hB[64];
+    for (int t = -1; t <= p.T; ++t)
+        if (!step_body<PAIRS, true>(p, c, lds, t, s64, pre, hB, hpre)) break;
+}
+
+__global__ __launch_bounds__(NTHREADS) void nicnes_decode_steps_screen_es_kernel(DecodeParams p0, ParentArgs pa,
+                                                                                 ScreenArgs sa) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const DecodeParams p = es_params(p0, pa);
+    const Ctx c = make_ctx(p);
+    Stage64Regs s64;
+    bool pre = false, hpre = false;
+    float hB[64];
+    for (int t = -1; t <= p.T; ++t)
+        if (!step_body<true, true, false, false, true>(p, c, lds, t, s64, pre, hB, hpre, nullptr, &sa)) break;
 }
 
 // ========== split path: one member step over several workgroups =================================
@@ -3285,6 +3204,10 @@ extern "C" hipError_t nicnes_decode_init() {
         {(const void*)nicnes_decode_steps_screen_kernel, LDS_SCREEN},
         {(const void*)nicnes_decode_steps_mut_kernel<true>, LDS64},
         {(const void*)nicnes_decode_steps_mut_kernel<false>, LDS64},
+        {(const void*)nicnes_decode_img64_es_kernel, LDS64},
+        {(const void*)nicnes_decode_steps_es_kernel<true>, LDS64},
+        {(const void*)nicnes_decode_steps_es_kernel<false>, LDS64},
+        {(const void*)nicnes_decode_steps_screen_es_kernel, LDS_SCREEN},
         {(const void*)nicnes_decode_logit_kernel<4, true>, LDS64},
         {(const void*)nicnes_decode_logit_kernel<4, false>, LDS64},
         {(const void*)nicnes_decode_logit_kernel<2, true>, LDS64},
@@ -3323,12 +3246,13 @@ extern "C" hipError_t nicnes_decode_occupancy(int* coop_per_cu, int* sample_per_
                                                         NTHREADS, LDS64);
 }
 
-extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead* mh, ScreenArgs* sa) {
+extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead* mh, ScreenArgs* sa, ParentArgs* pa) {
     const size_t wg0 = (size_t)m0 * (size_t)nslabs;        // workgroup index wg = member * slabs + slab
     const size_t rows = (size_t)m0 * 2 * (size_t)p->B * (size_t)p->T;
     p->noise_idx += m0;
     if (mh && mh->head_idx) mh->head_idx += m0;
     if (p->member_batch) p->member_batch += m0;
+    if (pa && pa->parent_of) pa->parent_of += m0;
     p->seq += rows;
     if (p->lp) p->lp += rows;
     p->scratch += wg0 * (size_t)(2 * p->G) * (SCR_SLOTS * 64);   // make_ctx / make_sctx lane scratch
@@ -3471,6 +3395,23 @@ extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead*
         }
     }
     if (n_launch) *n_launch = ne;
+    return hipGetLastError();
+}
+
+extern "C" hipError_t nicnes_launch_decode_es(const DecodeParams* p, const ParentArgs* pa, int member_count, int nslabs,
+                                              hipStream_t stream, const ScreenArgs* sa) {
+    if (p->G != 4 || p->S != 1 || p->coop || p->sample_u) return hipErrorInvalidValue;
+    if (!pa || !pa->parents || !pa->parent_of || pa->stride < p->D) return hipErrorInvalidValue;
+    const dim3 block(NTHREADS), grid(member_count, nslabs);
+    const bool pairs = p->bounded_lse && p->lp == nullptr;
+    hipLaunchKernelGGL(nicnes_decode_img64_es_kernel, grid, block, LDS64, stream, *p, *pa);
+    if (pairs && sa && sa->cap && sa->norm) {
+        hipLaunchKernelGGL(nicnes_screen_norm_es_kernel, dim3(member_count), block, 0, stream, *p, *pa, *sa);
+        hipLaunchKernelGGL(nicnes_decode_steps_screen_es_kernel, grid, block, LDS_SCREEN, stream, *p, *pa, *sa);
+    } else if (pairs)
+        hipLaunchKernelGGL(nicnes_decode_steps_es_kernel<true>, grid, block, LDS64, stream, *p, *pa);
+    else
+        hipLaunchKernelGGL(nicnes_decode_steps_es_kernel<false>, grid, block, LDS64, stream, *p, *pa);
     return hipGetLastError();
 }
 

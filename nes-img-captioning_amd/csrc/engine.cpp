@@ -175,6 +175,28 @@ struct nicnes_handle {
     int64_t t_prev = 0;
     int theta_fp32_prev = 0;
     std::vector<nicnes_split*> splits;        // resident evaluation splits (nicnes_split_create), freed with the handle
+    struct nicnes_es* es = nullptr;           // nic_es state (nicnes_es_create), freed with the handle
+};
+
+// nic_es state: the parents of the generation being evaluated (ptab[cur]), the table the next generation is written
+// to, the podium's elites, and each row's SM-PROPORTIONAL statistics.
+struct nicnes_es {
+    int32_t max_parents = 0, max_elites = 0, n_parents = 0;
+    int64_t Dp = 0;
+    int cur = 0;
+    int mode = 0;                     // NICNES_MUTATION_PLAIN or _SCALE
+    float* ptab[2] = {nullptr, nullptr};
+    float* etab = nullptr;
+    float* pmean[2] = {nullptr, nullptr};   // [max_parents] mean|theta_p| of the tables' rows
+    int64_t* pzero[2] = {nullptr, nullptr}; // ... their exact zeros
+    float* emean = nullptr;
+    int64_t* ezero = nullptr;
+    double* part_sum = nullptr;       // nicnes_es_stats_scratch(max rows)
+    unsigned long long* part_zero = nullptr;
+    int32_t* parent_of = nullptr;     // [max_members] device copy of an evaluate's / an advance's parent slots
+    double* neg = nullptr;            // [2 max_members] select scratch
+    float* dbuf = nullptr;            // [max_members, Dp] delta' rows (allocated at the first proportional evaluate)
+    uint64_t* didx = nullptr;
 };
 
 // A resident evaluation split (nicnes_split_create): N images' fc rows, their references cooked WITHOUT the end token
@@ -242,6 +264,13 @@ void layout(const nicnes_config* c, int64_t* off) {
     off[7] = o; o += 5 * R * R;    // core.h2h.weight
     off[8] = o; o += 5 * R;        // core.h2h.bias
     off[9] = o;
+}
+
+// nicnes_es_load_theta: a table row widened into the fp64 master (defined first: the kernel below stays the last of
+// this file's code object)
+__global__ void f32_to_f64_kernel(const float* in, double* out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (double)in[i];
 }
 
 __global__ void f64_to_f32_kernel(const double* in, float* out, int64_t n) {
@@ -516,6 +545,7 @@ int nicnes_destroy(nicnes_handle* h) {
     if (!h->splits.empty()) (void)hipDeviceSynchronize();
     for (nicnes_split* sp : h->splits) split_free(sp);
     h->splits.clear();
+    (void)nicnes_es_free(h);
     void* bufs[] = {h->theta64, h->theta32, h->m, h->v, h->ref_keys, h->ref_vec, h->ref_count, h->ref_len2,
                     h->ref_norm, h->nidx, h->seq, h->lp, h->row_scores, h->dscratch, h->stats, h->partials, h->norms,
                     h->hash_keys, h->hash_vals, h->img_hkey, h->img_hrow, h->img_vr, h->alive, h->part,
@@ -2064,6 +2094,406 @@ int nicnes_decode_shape(nicnes_handle* h, int32_t B, int32_t count, int32_t* out
     out3_host[0] = G;
     out3_host[1] = ns;
     out3_host[2] = S;
+    return NICNES_OK;
+}
+
+// ---- nic_es (src/algorithm/nic_es/) -------------------------------------------------------------------------------
+// A caller's host int32 array checked against [0, bound) and copied to dst on s through the pinned ring of
+// stage_member_batch (no wait for queued GPU work).
+static int es_stage_i32(nicnes_handle* h, const int32_t* host, int count, int32_t bound, int32_t* dst, hipStream_t s,
+                        const char* what) {
+    for (int k = 0; k < count; ++k)
+        if (host[k] < 0 || host[k] >= bound) return fail(h, NICNES_ERR_INVALID, std::string(what) + " entry out of range");
+    const int slot = h->mb_next;
+    h->mb_next = (slot + 1) % MB_RING;
+    if (h->mb_used[slot]) HIPC(h, hipEventSynchronize(h->mb_ev[slot]));
+    std::memcpy(h->mb_pin[slot], host, (size_t)count * sizeof(int32_t));
+    HIPC(h, hipMemcpyAsync(dst, h->mb_pin[slot], (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPC(h, hipEventRecord(h->mb_ev[slot], s));
+    h->mb_used[slot] = true;
+    return NICNES_OK;
+}
+
+int nicnes_es_free(nicnes_handle* h) {
+    if (!h) return NICNES_ERR_INVALID;
+    nicnes_es* es = h->es;
+    if (!es) return NICNES_OK;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    void* bufs[] = {es->ptab[0], es->ptab[1], es->etab, es->pmean[0], es->pmean[1], es->pzero[0], es->pzero[1], es->emean,
+                    es->ezero, es->part_sum, es->part_zero, es->parent_of, es->neg, es->dbuf, es->didx};
+    for (void* q : bufs)
+        if (q) (void)hipFree(q);
+    delete es;
+    h->es = nullptr;
+    return NICNES_OK;
+}
+
+int nicnes_es_create(nicnes_handle* h, int32_t max_parents, int32_t max_elites) {
+    if (!h || max_parents < 1 || max_elites < 1 || max_elites > max_parents) return NICNES_ERR_INVALID;
+    if (h->es) return fail(h, NICNES_ERR_INVALID, "nicnes_es_create: the handle has an ES state (nicnes_es_free first)");
+    HIPC(h, hipSetDevice(h->device));
+    nicnes_es* es = new nicnes_es();
+    h->es = es;
+    es->max_parents = max_parents;
+    es->max_elites = max_elites;
+    es->Dp = (h->D + 63) / 64 * 64;
+    const size_t MP = (size_t)max_parents, ME = (size_t)max_elites, MM = (size_t)h->cfg.max_members;
+    int rc = NICNES_OK;
+    for (int t = 0; t < 2 && !rc; ++t) {
+        rc = dalloc(h, &es->ptab[t], MP * (size_t)es->Dp);
+        if (!rc) rc = dalloc(h, &es->pmean[t], MP);
+        if (!rc) rc = dalloc(h, &es->pzero[t], MP);
+    }
+    if (!rc) rc = dalloc(h, &es->etab, ME * (size_t)es->Dp);
+    if (!rc) rc = dalloc(h, &es->emean, ME);
+    if (!rc) rc = dalloc(h, &es->ezero, ME);
+    if (!rc) rc = dalloc(h, &es->part_sum, nicnes_es_stats_scratch(max_parents));
+    if (!rc) rc = dalloc(h, &es->part_zero, nicnes_es_stats_scratch(max_parents));
+    if (!rc) rc = dalloc(h, &es->parent_of, MM);
+    if (!rc) rc = dalloc(h, &es->neg, 2 * MM);
+    if (rc) {
+        (void)nicnes_es_free(h);
+        return rc;
+    }
+    // rows no one has set read as zeros (the pad columns D .. Dp are never read)
+    for (int t = 0; t < 2; ++t) {
+        HIPC(h, hipMemset(es->ptab[t], 0, MP * (size_t)es->Dp * sizeof(float)));
+        HIPC(h, hipMemset(es->pmean[t], 0, MP * sizeof(float)));
+        HIPC(h, hipMemset(es->pzero[t], 0, MP * sizeof(int64_t)));
+    }
+    HIPC(h, hipMemset(es->etab, 0, ME * (size_t)es->Dp * sizeof(float)));
+    HIPC(h, hipMemset(es->emean, 0, ME * sizeof(float)));
+    HIPC(h, hipMemset(es->ezero, 0, ME * sizeof(int64_t)));
+    HIPC(h, hipDeviceSynchronize());
+    return NICNES_OK;
+}
+
+#define ES_STATE(h)                                                                  \
+    if (!(h)) return NICNES_ERR_INVALID;                                             \
+    nicnes_es* es = (h)->es;                                                         \
+    if (!es) return fail((h), NICNES_ERR_INVALID, "nicnes_es_create first")
+
+int nicnes_es_set_mutation(nicnes_handle* h, int32_t mode) {
+    ES_STATE(h);
+    if (mode != NICNES_MUTATION_PLAIN && mode != NICNES_MUTATION_SCALE)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "nic_es mutation: the engine implements plain and SM-PROPORTIONAL");
+    es->mode = mode;
+    return NICNES_OK;
+}
+
+int nicnes_es_set_parent(nicnes_handle* h, int32_t slot, const float* theta32, void* stream) {
+    ES_STATE(h);
+    if (!theta32 || slot < 0 || slot >= es->max_parents) return fail(h, NICNES_ERR_INVALID, "parent slot out of range");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    float* row = es->ptab[es->cur] + (size_t)slot * (size_t)es->Dp;
+    HIPC(h, hipMemcpyAsync(row, theta32, (size_t)h->D * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPC(h, nicnes_launch_es_parent_stats(row, 1, es->Dp, h->D, es->part_sum, es->part_zero, es->pmean[es->cur] + slot,
+                                          es->pzero[es->cur] + slot, s));
+    return NICNES_OK;
+}
+
+int nicnes_es_set_parent_count(nicnes_handle* h, int32_t count) {
+    ES_STATE(h);
+    if (count < 1 || count > es->max_parents) return fail(h, NICNES_ERR_INVALID, "parent count out of [1, max_parents]");
+    es->n_parents = count;
+    return NICNES_OK;
+}
+
+// a row of table 0 (current parents) or 1 (elites), with its statistics
+static int es_row(nicnes_handle* h, nicnes_es* es, int table, int slot, float** row, float** mean, int64_t** zeros) {
+    if (table == 0 && slot >= 0 && slot < es->max_parents) {
+        *row = es->ptab[es->cur] + (size_t)slot * (size_t)es->Dp;
+        *mean = es->pmean[es->cur] + slot;
+        *zeros = es->pzero[es->cur] + slot;
+        return NICNES_OK;
+    }
+    if (table == 1 && slot >= 0 && slot < es->max_elites) {
+        *row = es->etab + (size_t)slot * (size_t)es->Dp;
+        *mean = es->emean + slot;
+        *zeros = es->ezero + slot;
+        return NICNES_OK;
+    }
+    return fail(h, NICNES_ERR_INVALID, "table (0 parents, 1 elites) or slot out of range");
+}
+
+int nicnes_es_get_row(nicnes_handle* h, int32_t table, int32_t slot, float* theta32_out, void* stream) {
+    ES_STATE(h);
+    if (!theta32_out) return NICNES_ERR_INVALID;
+    float *row, *mean;
+    int64_t* zeros;
+    if (int rc = es_row(h, es, table, slot, &row, &mean, &zeros)) return rc;
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipMemcpyAsync(theta32_out, row, (size_t)h->D * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return NICNES_OK;
+}
+
+int nicnes_es_row_stats(nicnes_handle* h, int32_t table, int32_t slot, float* mean_abs_out_host, int64_t* zeros_out_host,
+                        void* stream) {
+    ES_STATE(h);
+    float *row, *mean;
+    int64_t* zeros;
+    if (int rc = es_row(h, es, table, slot, &row, &mean, &zeros)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    if (mean_abs_out_host) HIPC(h, hipMemcpyAsync(mean_abs_out_host, mean, sizeof(float), hipMemcpyDeviceToHost, s));
+    if (zeros_out_host) HIPC(h, hipMemcpyAsync(zeros_out_host, zeros, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPC(h, hipStreamSynchronize(s));
+    return NICNES_OK;
+}
+
+int nicnes_es_set_elite(nicnes_handle* h, int32_t elite_slot, int32_t table, int32_t slot, void* stream) {
+    ES_STATE(h);
+    if (elite_slot < 0 || elite_slot >= es->max_elites) return fail(h, NICNES_ERR_INVALID, "elite slot out of range");
+    float *row, *mean;
+    int64_t* zeros;
+    if (int rc = es_row(h, es, table, slot, &row, &mean, &zeros)) return rc;
+    if (table == 1 && slot == elite_slot) return NICNES_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipMemcpyAsync(es->etab + (size_t)elite_slot * (size_t)es->Dp, row, (size_t)h->D * sizeof(float),
+                           hipMemcpyDeviceToDevice, s));
+    HIPC(h, hipMemcpyAsync(es->emean + elite_slot, mean, sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPC(h, hipMemcpyAsync(es->ezero + elite_slot, zeros, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    return NICNES_OK;
+}
+
+int nicnes_es_load_theta(nicnes_handle* h, int32_t table, int32_t slot, void* stream) {
+    ES_STATE(h);
+    float *row, *mean;
+    int64_t* zeros;
+    if (int rc = es_row(h, es, table, slot, &row, &mean, &zeros)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipMemcpyAsync(h->theta32, row, (size_t)h->D * sizeof(float), hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(f32_to_f64_kernel, dim3((unsigned)((h->D + 255) / 256)), dim3(256), 0, s, h->theta32, h->theta64,
+                       h->D);
+    HIPC(h, hipGetLastError());
+    h->theta_is_fp32 = 1;
+    h->step_pending_check = false;
+    h->theta_set = true;
+    return NICNES_OK;
+}
+
+// the arguments of the materialise kernel common to an advance and a single offspring
+static EsMaterialise es_mat_args(const nicnes_handle* h, const nicnes_es* es, uint64_t generation, float sigma) {
+    EsMaterialise a{};
+    a.noise = h->noise;
+    a.parents = es->ptab[es->cur];
+    a.mean_abs = es->pmean[es->cur];
+    a.elites = es->etab;
+    a.stride = es->Dp;
+    a.dim = h->D;
+    a.seed = h->cfg.noise_seed;
+    a.generation = generation;
+    a.table_len = h->cfg.noise_len;
+    a.sigma = sigma;
+    a.mode = es->mode;
+    return a;
+}
+
+int nicnes_es_offspring(nicnes_handle* h, uint64_t generation, int32_t pair, int32_t sign, float sigma, int32_t parent,
+                        float* theta32_out, void* stream) {
+    ES_STATE(h);
+    if (!theta32_out || pair < 0 || (sign != 0 && sign != 1)) return NICNES_ERR_INVALID;
+    if (parent < 0 || parent >= es->n_parents) return fail(h, NICNES_ERR_INVALID, "parent outside [0, parent count)");
+    if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
+    HIPC(h, hipSetDevice(h->device));
+    EsMaterialise a = es_mat_args(h, es, generation, sigma);
+    a.out = theta32_out;
+    a.pair0 = pair;
+    a.sign0 = sign;
+    a.parent0 = parent;
+    HIPC(h, nicnes_launch_es_materialise(&a, 1, (hipStream_t)stream));
+    return NICNES_OK;
+}
+
+int nicnes_es_select(nicnes_handle* h, const double* fitness, int32_t n, int32_t n_keep, int32_t* order_out,
+                     void* stream) {
+    ES_STATE(h);
+    if (!fitness || !order_out) return NICNES_ERR_INVALID;
+    if (n < 1 || n > 2 * h->cfg.max_members) return fail(h, NICNES_ERR_INVALID, "n out of [1, 2 max_members]");
+    if (n_keep < 1 || n_keep > n) return fail(h, NICNES_ERR_INVALID, "n_keep out of [1, n]");
+    HIPC(h, hipSetDevice(h->device));
+    // (the rank scratch holds nicnes_rank_scratch_pairs(2 max_members) pairs from nicnes_create on)
+    HIPC(h, nicnes_launch_es_select(fitness, n, n_keep, es->neg, h->rank_key, h->rank_idx, order_out, (hipStream_t)stream));
+    return NICNES_OK;
+}
+
+int nicnes_es_advance(nicnes_handle* h, uint64_t generation, float sigma, const int32_t* parent_of_host, int32_t n_pairs,
+                      const int32_t* order, int32_t n_keep, int32_t n_front, void* stream) {
+    ES_STATE(h);
+    if (!parent_of_host || !order) return NICNES_ERR_INVALID;
+    if (n_pairs < 1 || n_pairs > h->cfg.max_members) return fail(h, NICNES_ERR_INVALID, "n_pairs out of [1, max_members]");
+    if (n_keep < 1 || n_keep > 2 * n_pairs || n_front < 0 || n_front > es->max_elites ||
+        n_front + n_keep > es->max_parents)
+        return fail(h, NICNES_ERR_INVALID, "n_keep / n_front: out of range or beyond max_parents");
+    if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    if (int rc = es_stage_i32(h, parent_of_host, n_pairs, es->n_parents, es->parent_of, s, "parent_of")) return rc;
+    const int nxt = 1 - es->cur, rows = n_front + n_keep;
+    EsMaterialise a = es_mat_args(h, es, generation, sigma);
+    a.parent_of = es->parent_of;
+    a.order = order;
+    a.out = es->ptab[nxt];
+    a.n_front = n_front;
+    a.n_pairs = n_pairs;
+    HIPC(h, nicnes_launch_es_materialise(&a, rows, s));
+    HIPC(h, nicnes_launch_es_parent_stats(es->ptab[nxt], rows, es->Dp, h->D, es->part_sum, es->part_zero, es->pmean[nxt],
+                                          es->pzero[nxt], s));
+    es->cur = nxt;
+    es->n_parents = rows;
+    return NICNES_OK;
+}
+
+int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin, int32_t count, float sigma,
+                       const int32_t* parent_of_host, const int32_t* member_batch_host, double* fitness_out,
+                       int32_t* seq_out, float* logprob_out, void* stream) {
+    ES_STATE(h);
+    if (!fitness_out || !parent_of_host || pair_begin < 0) return NICNES_ERR_INVALID;
+    const int mode = h->fitness_mode;
+    if (mode >= NICNES_FITNESS_SAMPLE)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "nic_es: the sampled fitness modes are not implemented (greedy, greedy_*)");
+    if ((h->dec_S != 0 && h->dec_S != 1) || (h->dec_G != 0 && h->dec_G != 4))
+        return fail(h, NICNES_ERR_UNSUPPORTED, "nic_es decodes on the fused path only: nicnes_set_decode_split(1, 4) or (0, 0)");
+    if (count < 1 || count > h->cfg.max_members) return fail(h, NICNES_ERR_INVALID, "count out of [1, max_members]");
+    if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
+    if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
+    if (es->n_parents < 1) return fail(h, NICNES_ERR_INVALID, "nicnes_es_set_parent_count first");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    const int32_t* mb = nullptr;
+    if (int rc = stage_member_batch(h, member_batch_host, count, s, &mb)) return rc;
+    if (int rc = es_stage_i32(h, parent_of_host, count, es->n_parents, es->parent_of, s, "parent_of")) return rc;
+    HIPC(h, nicnes_launch_noise_index(h->cfg.noise_seed, generation, (uint64_t)pair_begin, count, h->cfg.noise_len,
+                                      (uint64_t)h->D, h->nidx, s));
+    DecodeParams p{};
+    p.theta = es->ptab[es->cur];       // (every *_es kernel sets its workgroup's base from ParentArgs)
+    if (es->mode) {
+        if (!es->dbuf) {               // first proportional evaluate: [max_members, Dp] delta' rows, as dbuf
+            HIPC(h, hipDeviceSynchronize());
+            int rc = dalloc(h, &es->dbuf, (size_t)h->cfg.max_members * (size_t)es->Dp);
+            if (!rc) rc = dalloc(h, &es->didx, (size_t)h->cfg.max_members);
+            if (rc) return rc;
+            HIPC(h, nicnes_launch_iota_stride(es->didx, h->cfg.max_members, (uint64_t)es->Dp, s));
+        }
+        HIPC(h, nicnes_launch_es_mutate(h->noise, h->nidx, count, es->ptab[es->cur], es->parent_of, es->pmean[es->cur],
+                                        es->Dp, h->D, sigma, es->dbuf, s));
+        p.noise = es->dbuf;
+        p.noise_idx = es->didx;
+    } else {                           // plain: the sigma-scaled table, as nicnes_evaluate
+        if (!h->noise_sc) {
+            HIPC(h, hipDeviceSynchronize());
+            int rc = dalloc(h, &h->noise_sc, (size_t)h->cfg.noise_len);
+            if (rc) return rc;
+        }
+        if (!h->sc_valid || __builtin_bit_cast(uint32_t, h->sc_sigma) != __builtin_bit_cast(uint32_t, sigma)) {
+            HIPC(h, nicnes_launch_scale(h->noise, h->noise_sc, h->cfg.noise_len, sigma, s));
+            h->sc_sigma = sigma;
+            h->sc_valid = true;
+        }
+        p.noise = h->noise_sc;
+        p.noise_idx = h->nidx;
+    }
+    p.fc = h->fc;
+    p.member_batch = mb;
+    p.seq = seq_out ? seq_out : h->seq;
+    const bool crit_lp = mode >= NICNES_FITNESS_GREEDY_LOGPROB && mode <= NICNES_FITNESS_GREEDY_AVGPROB;
+    p.lp = logprob_out ? logprob_out : (crit_lp ? h->lp : nullptr);
+    p.scratch = h->dscratch;
+    p.stats = h->stats;
+    p.alive = h->alive;
+    p.force_exact = h->force_exact;
+    p.lse_margin = h->lse_margin;
+    // the bounded-lse policy and the fault read-back of evaluate_impl
+    if (h->stats_pending && hipEventQuery(h->stats_ev) == hipSuccess) {
+        const int32_t fb = h->stats_host[0];
+        if (h->stats_host[2] != 0 || h->stats_host[3] != 0)
+            return fail(h, NICNES_ERR_FAULT, "a decode on this handle lost rows (nicnes_stats, nicnes_clear_faults)");
+        if (h->last_bounded && fb - h->fb_seen >= 2) h->exact_left = 32;
+        h->fb_seen = fb;
+        h->stats_pending = false;
+    }
+    const bool bounded = h->bounded_mode == 1 || (h->bounded_mode == 2 && h->exact_left == 0);
+    if (h->bounded_mode == 2 && h->exact_left > 0 && !p.lp) --h->exact_left;
+    p.bounded_lse = bounded ? 1 : 0;
+    h->last_decode_bounded = (bounded && !p.lp) ? 1 : 0;
+    const int rows = h->B, nslabs = nslabs_of(rows, 4);
+    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr};
+    const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)count * nslabs >= h->n_cu);
+    if (screen_on && !p.lp && bounded && h->screen_cap && h->screen_norm && (int64_t)count * nslabs <= h->screen_wgs) {
+        sa.cap = h->screen_cap;
+        sa.norm = h->screen_norm;
+    }
+    p.G = 4;
+    p.S = 1;
+    p.part = h->part;
+    p.no_exit = (p.lp && nslabs > 1) ? 1 : 0;
+    p.coop_ctr = h->coop_ctr;
+    p.alive2 = h->alive + h->alive_stride;
+    p.alive_stride = h->alive_stride;
+    p.B = rows;
+    p.B_img = h->B;
+    p.rpi = 1;
+    p.F = h->cfg.fc_feat_size;
+    p.V1 = h->V1;
+    p.T = h->cfg.seq_length;
+    p.D = h->D;
+    p.off_img_w = h->off[0];
+    p.off_img_b = h->off[1];
+    p.off_emb_w = h->off[2];
+    p.off_log_w = h->off[3];
+    p.off_log_b = h->off[4];
+    p.off_i2h_w = h->off[5];
+    p.off_i2h_b = h->off[6];
+    p.off_h2h_w = h->off[7];
+    p.off_h2h_b = h->off[8];
+    const size_t out_rows = (size_t)count * 2 * rows;
+    HIPC(h, hipMemsetAsync(p.seq, 0, out_rows * h->cfg.seq_length * sizeof(int32_t), s));
+    if (p.lp) HIPC(h, hipMemsetAsync(p.lp, 0, out_rows * h->cfg.seq_length * sizeof(float), s));
+    if (h->timing) HIPC(h, hipEventRecord(h->ev[0], s));
+    ParentArgs pa{es->ptab[es->cur], es->parent_of, es->Dp};
+    // the pairs in parts on the engine's streams when nicnes_set_decode_streams asks for it (as launch_decode_parts)
+    const int nstr = std::min(count, std::max(h->dec_streams, 1));
+    if (nstr > 1) {
+        if (!h->ev_fork) HIPC(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+        for (int i = 0; i < nstr - 1; ++i)
+            if (!h->sx[i]) {
+                HIPC(h, hipStreamCreateWithFlags(&h->sx[i], hipStreamNonBlocking));
+                HIPC(h, hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
+            }
+        HIPC(h, hipEventRecord(h->ev_fork, s));
+        for (int i = 0; i < nstr; ++i) {
+            const int a = (int)((int64_t)count * i / nstr), b = (int)((int64_t)count * (i + 1) / nstr);
+            DecodeParams pi = p;
+            ScreenArgs si_ = sa;
+            ParentArgs pai = pa;
+            nicnes_decode_shift(&pi, a, nslabs, nullptr, &si_, &pai);
+            hipStream_t si = i == 0 ? s : h->sx[i - 1];
+            if (i > 0) HIPC(h, hipStreamWaitEvent(si, h->ev_fork, 0));
+            HIPC(h, nicnes_launch_decode_es(&pi, &pai, b - a, nslabs, si, &si_));
+        }
+        for (int i = 0; i < nstr - 1; ++i) {
+            HIPC(h, hipEventRecord(h->ev_join[i], h->sx[i]));
+            HIPC(h, hipStreamWaitEvent(s, h->ev_join[i], 0));
+        }
+    } else {
+        HIPC(h, nicnes_launch_decode_es(&p, &pa, count, nslabs, s, &sa));
+    }
+    h->n_dev = 0;
+    h->multi_stream = nstr > 1;
+    if (p.no_exit) HIPC(h, nicnes_launch_lp_batch_exit(p.seq, p.lp, 2 * count, rows, h->cfg.seq_length, s));
+    if (h->timing) HIPC(h, hipEventRecord(h->ev[1], s));
+    if (!h->stats_pending) {
+        HIPC(h, hipMemcpyAsync(h->stats_host, h->stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPC(h, hipEventRecord(h->stats_ev, s));
+        h->stats_pending = true;
+        h->last_bounded = bounded && !p.lp;
+    }
+    if (int rc = score_rollouts(h, p.seq, p.lp, 2 * count, rows, 1, mb, nullptr, fitness_out, nullptr, s)) return rc;
+    if (h->timing) HIPC(h, hipEventRecord(h->ev[2], s));
     return NICNES_OK;
 }
 

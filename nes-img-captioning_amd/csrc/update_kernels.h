@@ -50,3 +50,33 @@ extern "C" int nicnes_adam_blocks(int64_t dim);
 extern "C" hipError_t nicnes_launch_adam(const AdamParams* p, double* norms_out, hipStream_t s);
 // out[i] = fp32(sigma * in[i]), i < n (the decode's sigma-scaled noise table)
 extern "C" hipError_t nicnes_launch_scale(const float* in, float* out, uint64_t n, float sigma, hipStream_t s);
+
+// ---- nic_es (the generation step; update_kernels.hip) ----
+// delta' rows of `count` pairs over their parents (SM-PROPORTIONAL): out [count, stride]
+extern "C" hipError_t nicnes_launch_es_mutate(const float* noise, const uint64_t* idx, int count, const float* parents,
+                                              const int32_t* parent_of, const float* mean_abs, int64_t stride,
+                                              int64_t dim, float sigma, float* out, hipStream_t s);
+// mean|theta| (fp32 of an fp64 sum in a fixed order) and the zero count of `rows` table rows; part_sum / part_zero:
+// nicnes_es_stats_scratch(rows) entries each
+extern "C" size_t nicnes_es_stats_scratch(int rows);
+extern "C" hipError_t nicnes_launch_es_parent_stats(const float* table, int rows, int64_t stride, int64_t dim,
+                                                    double* part_sum, unsigned long long* part_zero, float* mean_out,
+                                                    int64_t* zeros_out, hipStream_t s);
+// the first n_keep offspring ids in descending fitness (ties to the lower id, NaN last); neg [n] fp64 scratch,
+// skey / sidx: nicnes_rank_scratch_pairs(n) entries
+extern "C" hipError_t nicnes_launch_es_select(const double* fit, int n, int n_keep, double* neg, uint64_t* skey,
+                                              uint32_t* sidx, int32_t* order_out, hipStream_t s);
+struct EsMaterialise {
+    const float* noise;
+    const float* parents;        // current table
+    const float* mean_abs;       // its rows' mean|theta|
+    const float* elites;
+    const int32_t* parent_of;    // [pairs]
+    const int32_t* order;        // [n_keep] offspring ids, or NULL
+    float* out;                  // the other table (or one row)
+    int64_t stride, dim;
+    uint64_t seed, generation, table_len;
+    float sigma;
+    int32_t mode, n_front, n_pairs, pair0, sign0, parent0;
+};
+extern "C" hipError_t nicnes_launch_es_materialise(const EsMaterialise* a, int rows, hipStream_t s);

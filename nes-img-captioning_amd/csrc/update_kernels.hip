@@ -491,6 +491,193 @@ extern "C" hipError_t nicnes_launch_scale(const float* in, float* out, uint64_t 
     return hipGetLastError();
 }
 
+// ---- nic_es: the generation step on the device (src/algorithm/nic_es/) ---------------------------------------------
+// An offspring is (parent slot, noise index, sign); the kernels below form the perturbation rows the decode reads,
+// order a generation's fitness, and write the survivors into the other parent table. The reference does all of it
+// through .pth files (ESWorker.fitness nic_es_worker.py:118-170, ESIteration.record_parents iterations.py).
+
+// a_p[j] of SM-PROPORTIONAL with the parent as param_vector (nets.py:107-111): |theta_p[j]|, or mean|theta_p| at an
+// exact zero (either sign); delta'[j] = fp32(fp32(sigma z) * a)
+__device__ __forceinline__ float es_delta(float z, float sigma, float th, float mean_abs, int mode) {
+    const float d = sigma * z;
+    if (mode == 0) return d;
+    const float a = th == 0.f ? mean_abs : __builtin_fabsf(th);
+    return d * a;
+}
+
+// delta' rows of `count` pairs: out row k = the pair's whole perturbation over its parent parent_of[k]
+__global__ __launch_bounds__(256) void nicnes_es_mutate_kernel(const float* __restrict__ noise,
+                                                               const uint64_t* __restrict__ idx,
+                                                               const float* __restrict__ parents,
+                                                               const int32_t* __restrict__ parent_of,
+                                                               const float* __restrict__ mean_abs, int64_t stride,
+                                                               int64_t dim, float sigma, float* __restrict__ out) {
+    const int k = blockIdx.y;
+    const int32_t pi = parent_of[k];
+    const float* z = noise + idx[k];
+    const float* th = parents + (int64_t)pi * stride;
+    const float mean = mean_abs[pi];
+    float* o = out + (int64_t)k * stride;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = dim / 4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += step) {
+        f32x4 zv, r;
+        __builtin_memcpy(&zv, z + 4 * i, 16);               // slice starts are multiples of 64 floats
+        const f32x4 tv = reinterpret_cast<const f32x4*>(th)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = es_delta(zv[e], sigma, tv[e], mean, 2);
+        __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(o) + i);
+    }
+    for (int64_t j = 4 * n4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < dim; j += step)
+        o[j] = es_delta(z[j], sigma, th[j], mean, 2);
+}
+
+extern "C" hipError_t nicnes_launch_es_mutate(const float* noise, const uint64_t* idx, int count, const float* parents,
+                                              const int32_t* parent_of, const float* mean_abs, int64_t stride,
+                                              int64_t dim, float sigma, float* out, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(nicnes_es_mutate_kernel, dim3(512, count), dim3(256), 0, s, noise, idx, parents, parent_of,
+                       mean_abs, stride, dim, sigma, out);
+    return hipGetLastError();
+}
+
+// mean|theta_p| and the zero count of `rows` table rows: workgroup (b, r) sums the b-th of ES_STAT_BLOCKS contiguous
+// ranges of row r in fp64 (each thread its strided elements in order, then a tree over the threads), and the last
+// pass adds the ES_STAT_BLOCKS partials in index order and rounds sum / dim to fp32 once. A fixed order, no floating
+// atomics: the same bits on every run.
+#define ES_STAT_BLOCKS 64
+__global__ __launch_bounds__(256) void nicnes_es_parent_stats_kernel(const float* __restrict__ table, int64_t stride,
+                                                                     int64_t dim, double* __restrict__ part_sum,
+                                                                     unsigned long long* __restrict__ part_zero) {
+    __shared__ double rs[256];
+    __shared__ unsigned long long rz[256];
+    const int r = blockIdx.y, b = blockIdx.x;
+    const float* th = table + (int64_t)r * stride;
+    const int64_t per = (dim + ES_STAT_BLOCKS - 1) / ES_STAT_BLOCKS;
+    const int64_t j0 = (int64_t)b * per, j1 = j0 + per < dim ? j0 + per : dim;
+    double a = 0.0;
+    unsigned long long zc = 0;
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) {
+        const float t = th[j];
+        a += (double)__builtin_fabsf(t);
+        zc += t == 0.f ? 1ull : 0ull;
+    }
+    rs[threadIdx.x] = a;
+    rz[threadIdx.x] = zc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            rs[threadIdx.x] += rs[threadIdx.x + o];
+            rz[threadIdx.x] += rz[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part_sum[(int64_t)r * ES_STAT_BLOCKS + b] = rs[0];
+        part_zero[(int64_t)r * ES_STAT_BLOCKS + b] = rz[0];
+    }
+}
+
+__global__ void nicnes_es_parent_stats_finish_kernel(const double* part_sum, const unsigned long long* part_zero,
+                                                     int rows, int64_t dim, float* mean_out, int64_t* zeros_out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    double a = 0.0;
+    unsigned long long zc = 0;
+    for (int b = 0; b < ES_STAT_BLOCKS; ++b) {
+        a += part_sum[(int64_t)r * ES_STAT_BLOCKS + b];
+        zc += part_zero[(int64_t)r * ES_STAT_BLOCKS + b];
+    }
+    mean_out[r] = (float)(a / (double)dim);
+    zeros_out[r] = (int64_t)zc;
+}
+
+extern "C" size_t nicnes_es_stats_scratch(int rows) { return (size_t)rows * ES_STAT_BLOCKS; }
+
+extern "C" hipError_t nicnes_launch_es_parent_stats(const float* table, int rows, int64_t stride, int64_t dim,
+                                                    double* part_sum, unsigned long long* part_zero, float* mean_out,
+                                                    int64_t* zeros_out, hipStream_t s) {
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(nicnes_es_parent_stats_kernel, dim3(ES_STAT_BLOCKS, rows), dim3(256), 0, s, table, stride, dim,
+                       part_sum, part_zero);
+    hipLaunchKernelGGL(nicnes_es_parent_stats_finish_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, part_sum, part_zero,
+                       rows, dim, mean_out, zeros_out);
+    return hipGetLastError();
+}
+
+// Truncation selection (ESMaster.run_master / ESIteration.record_parents sort the offspring by score): the offspring
+// ids (2 pair + sign, the position in the [pairs, 2] fitness) in descending fitness, ties to the lower id, NaN last,
+// -0 == +0. That is the rank sort's ascending (value, index) order of the negated fitness, so the sort is the rank
+// sort's: nicnes_rank_sort_kernel orders each chunk of RANK_CHUNK in LDS, and an entry's place is the sum of its lower
+// bounds over the chunks (keys are unique with the id). order_out[r] = the id in place r, for r < n_keep.
+__global__ void nicnes_es_negate_kernel(const double* fit, int n, double* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = -fit[i];
+}
+
+__global__ __launch_bounds__(256) void nicnes_es_order_kernel(const double* neg, int n, const uint64_t* skey,
+                                                              const uint32_t* sidx, int n_keep, int32_t* order_out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const int nchunks = (n + RANK_CHUNK - 1) / RANK_CHUNK;
+    const uint64_t kq = rank_key(neg[e]);
+    int rank = 0;
+    for (int c = 0; c < nchunks; ++c)
+        rank += chunk_lower_bound(skey + (size_t)c * RANK_CHUNK, sidx + (size_t)c * RANK_CHUNK, kq, (uint32_t)e);
+    if (rank < n_keep) order_out[rank] = e;
+}
+
+extern "C" hipError_t nicnes_launch_es_select(const double* fit, int n, int n_keep, double* neg, uint64_t* skey,
+                                              uint32_t* sidx, int32_t* order_out, hipStream_t s) {
+    const int nchunks = (n + RANK_CHUNK - 1) / RANK_CHUNK;
+    hipLaunchKernelGGL(nicnes_es_negate_kernel, dim3((n + 255) / 256), dim3(256), 0, s, fit, n, neg);
+    hipLaunchKernelGGL(nicnes_rank_sort_kernel, dim3(nchunks), dim3(RANK_CHUNK / 2), 0, s, neg, n, skey, sidx);
+    hipLaunchKernelGGL(nicnes_es_order_kernel, dim3((n + 255) / 256), dim3(256), 0, s, neg, n, skey, sidx, n_keep,
+                       order_out);
+    return hipGetLastError();
+}
+
+// The next parent table: row r < n_front is elite row r; row n_front + i is the offspring order[i] = 2 pair + sign,
+// fp32(theta_p + delta') or fp32(theta_p - delta') with p = parent_of[pair] in the CURRENT table and delta' re-formed
+// from the noise table (the formula and roundings of the decode's w + z / w - z over nicnes_es_mutate_kernel's rows, so
+// the bits are the decoded offspring's). With order == NULL the one offspring (pair0, sign0, parent0) is written to row
+// 0 (nicnes_es_offspring).
+__global__ __launch_bounds__(256) void nicnes_es_materialise_kernel(EsMaterialise a) {
+    const int r = blockIdx.y;
+    float* o = a.out + (int64_t)r * a.stride;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x, j0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a.order && r < a.n_front) {
+        const float* e = a.elites + (int64_t)r * a.stride;
+        for (int64_t j = j0; j < a.dim; j += step) o[j] = e[j];
+        return;
+    }
+    int pair = a.pair0, sign = a.sign0, pi = a.parent0;
+    if (a.order) {
+        const int32_t id = a.order[r - a.n_front];
+        if ((uint32_t)id >= 2u * (uint32_t)a.n_pairs) {          // not an offspring of this generation: a NaN row
+            for (int64_t j = j0; j < a.dim; j += step) o[j] = __builtin_nanf("");
+            return;
+        }
+        pair = id >> 1;
+        sign = id & 1;
+        pi = a.parent_of[pair];
+    }
+    const float* z = a.noise + nn_noise_index(a.seed, a.generation, (uint64_t)pair, a.table_len, (uint64_t)a.dim);
+    const float* th = a.parents + (int64_t)pi * a.stride;
+    const float mean = a.mode ? a.mean_abs[pi] : 0.f;
+    for (int64_t j = j0; j < a.dim; j += step) {
+        const float t = th[j], d = es_delta(z[j], a.sigma, t, mean, a.mode);
+        o[j] = sign ? t - d : t + d;
+    }
+}
+
+extern "C" hipError_t nicnes_launch_es_materialise(const EsMaterialise* a, int rows, hipStream_t s) {
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(nicnes_es_materialise_kernel, dim3(256, rows), dim3(256), 0, s, *a);
+    return hipGetLastError();
+}
+
+// (the last kernel of this file stays the last: its code object ends with it)
 __global__ void nicnes_iota_stride_kernel(uint64_t* out, int n, uint64_t stride) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (uint64_t)i * stride;

@@ -26,7 +26,11 @@ EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_create', 'nicne
            'nicnes_last_decode_lse', 'nicnes_test_logit_chain', 'nicnes_test_score_rows',
            'nicnes_test_certify_items', 'nicnes_test_certify_items_owned',
            'nicnes_set_decode_screen', 'nicnes_screen_stats', 'nicnes_split_create', 'nicnes_split_destroy',
-           'nicnes_split_decode', 'nicnes_split_score', 'nicnes_split_evaluate']
+           'nicnes_split_decode', 'nicnes_split_score', 'nicnes_split_evaluate',
+           'nicnes_es_create', 'nicnes_es_free', 'nicnes_es_set_mutation', 'nicnes_es_set_parent',
+           'nicnes_es_set_parent_count', 'nicnes_es_get_row', 'nicnes_es_row_stats', 'nicnes_es_evaluate',
+           'nicnes_es_offspring', 'nicnes_es_select', 'nicnes_es_advance', 'nicnes_es_set_elite',
+           'nicnes_es_load_theta']
 
 
 class NicnesConfig(ctypes.Structure):
@@ -113,6 +117,19 @@ def lib(path=None):
         'nicnes_split_decode': (c.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         'nicnes_split_score': (c.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
         'nicnes_split_evaluate': (c.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+        'nicnes_es_create': (c.c_int, [vp, i32, i32]),
+        'nicnes_es_free': (c.c_int, [vp]),
+        'nicnes_es_set_mutation': (c.c_int, [vp, i32]),
+        'nicnes_es_set_parent': (c.c_int, [vp, i32, vp, vp]),
+        'nicnes_es_set_parent_count': (c.c_int, [vp, i32]),
+        'nicnes_es_get_row': (c.c_int, [vp, i32, i32, vp, vp]),
+        'nicnes_es_row_stats': (c.c_int, [vp, i32, i32, vp, vp, vp]),
+        'nicnes_es_evaluate': (c.c_int, [vp, u64, i32, i32, f32, vp, vp, vp, vp, vp, vp]),
+        'nicnes_es_offspring': (c.c_int, [vp, u64, i32, i32, f32, i32, vp, vp]),
+        'nicnes_es_select': (c.c_int, [vp, vp, i32, i32, vp, vp]),
+        'nicnes_es_advance': (c.c_int, [vp, u64, f32, vp, i32, vp, i32, i32, vp]),
+        'nicnes_es_set_elite': (c.c_int, [vp, i32, i32, i32, vp]),
+        'nicnes_es_load_theta': (c.c_int, [vp, i32, i32, vp]),
         'nicnes_comm_unique_id': (c.c_int, [vp]),
         'nicnes_comm_init': (c.c_int, [vp, i32, i32, vp]),
         'nicnes_comm_attach': (c.c_int, [vp, vp]),

@@ -494,6 +494,123 @@ class Engine:
         check(self.L.nicnes_decode_shape(self.h, int(B or self.B), int(count), out), self.h, 'decode_shape')
         return tuple(int(v) for v in out)
 
+    # ---------------------------------------------------------------- nic_es (nicnes_es_*) -----
+    ES_TABLES = {'parents': 0, 'elites': 1}
+
+    def es_create(self, max_parents, max_elites=1):
+        """The ES state on this handle: two parent tables of max_parents rows and an elite table."""
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_es_create(self.h, int(max_parents), int(max_elites)), self.h, 'es_create')
+
+    def es_free(self):
+        check(self.L.nicnes_es_free(self.h), self.h, 'es_free')
+
+    def es_set_mutation(self, mode='plain'):
+        """'plain' or 'scale' (SM-PROPORTIONAL over each pair's own parent); anything else is not supported."""
+        code = self.MUTATION_MODES[mode] if isinstance(mode, str) else int(mode)
+        check(self.L.nicnes_es_set_mutation(self.h, code), self.h, 'es_set_mutation')
+
+    def es_set_parent(self, slot, theta):
+        t = self._dev(theta, torch.float32)
+        if t.numel() != self.D:
+            raise ValueError('a parent needs D entries')
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_es_set_parent(self.h, int(slot), _ptr(t), self._stream()), self.h, 'es_set_parent')
+            torch.cuda.current_stream().synchronize()    # t stays alive until the copy has run
+
+    def es_set_parents(self, thetas):
+        """Parent slots 0 .. len(thetas) - 1 and the parent count."""
+        for i, t in enumerate(thetas):
+            self.es_set_parent(i, t)
+        self.es_set_parent_count(len(thetas))
+
+    def es_set_parent_count(self, n):
+        check(self.L.nicnes_es_set_parent_count(self.h, int(n)), self.h, 'es_set_parent_count')
+
+    def es_row(self, slot, table='parents'):
+        """Row `slot` of the current parent table or of the elite table: fp32 [D] on the GPU."""
+        out = torch.empty(self.D, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_es_get_row(self.h, self.ES_TABLES[table], int(slot), _ptr(out), self._stream()), self.h,
+                  'es_get_row')
+        return out
+
+    def es_row_stats(self, slot, table='parents'):
+        """(fp32 mean|theta|, exact zeros) of a row, as SM-PROPORTIONAL uses them (synchronises)."""
+        m, z = ctypes.c_float(), ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_es_row_stats(self.h, self.ES_TABLES[table], int(slot), ctypes.byref(m), ctypes.byref(z),
+                                             self._stream()), self.h, 'es_row_stats')
+        return np.float32(m.value), int(z.value)
+
+    @staticmethod
+    def _host_i32(a, n, what):
+        a = np.ascontiguousarray(np.asarray(a, np.int32))
+        if a.shape != (n,):
+            raise ValueError('%s needs %d entries' % (what, n))
+        return a
+
+    def es_evaluate(self, generation, pair_begin, count, sigma, parent_of, fitness_out=None, return_seq=False,
+                    return_lp=False, member_batch=None):
+        """Fitness of the offspring of pairs [pair_begin, +count) of `generation`: [count, 2] fp64 on the GPU (offspring
+        2k = parent_of[k] + delta'_k, 2k + 1 = parent_of[k] - delta'_k). parent_of: the parent slot of each pair of
+        the slice (host ints). return_seq / return_lp / member_batch as evaluate()."""
+        fit = fitness_out if fitness_out is not None else torch.empty((count, 2), dtype=torch.float64,
+                                                                      device=self.device)
+        shape = (count, 2, self.B, self.cfg.seq_length)
+        seq = torch.empty(shape, dtype=torch.int32, device=self.device) if return_seq else None
+        lp = torch.empty(shape, dtype=torch.float32, device=self.device) if return_lp else None
+        po = self._host_i32(parent_of, count, 'parent_of')
+        mb = self._host_i32(member_batch, count, 'member_batch') if member_batch is not None else None
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_es_evaluate(self.h, ctypes.c_uint64(generation), int(pair_begin), int(count),
+                                            ctypes.c_float(sigma), po.ctypes.data_as(ctypes.c_void_p),
+                                            mb.ctypes.data_as(ctypes.c_void_p) if mb is not None else None, _ptr(fit),
+                                            _ptr(seq), _ptr(lp), self._stream()), self.h, 'es_evaluate')
+        out = (fit,) + ((seq,) if return_seq else ()) + ((lp,) if return_lp else ())
+        return out if len(out) > 1 else fit
+
+    def es_offspring(self, generation, pair, sign, sigma, parent):
+        """fp32 theta [D] (GPU) of offspring (pair, sign: 0 +, 1 -) of `generation` over parent slot `parent`."""
+        out = torch.empty(self.D, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_es_offspring(self.h, ctypes.c_uint64(generation), int(pair), int(sign),
+                                             ctypes.c_float(sigma), int(parent), _ptr(out), self._stream()), self.h,
+                  'es_offspring')
+        return out
+
+    def es_select(self, fitness, n_keep):
+        """The first n_keep offspring ids (2 pair + sign) in descending fitness (ties to the lower id, NaN last):
+        int32 [n_keep] on the GPU. fitness: any fp64 GPU tensor of n values ([pairs, 2] ravelled)."""
+        f = fitness.reshape(-1)
+        assert f.dtype == torch.float64 and f.is_contiguous()
+        out = torch.empty(max(int(n_keep), 1), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_es_select(self.h, _ptr(f), int(f.numel()), int(n_keep), _ptr(out), self._stream()),
+                  self.h, 'es_select')
+        return out[:n_keep]
+
+    def es_advance(self, generation, sigma, parent_of, order, n_front=0):
+        """The next parents: elite rows [0, n_front) + the offspring `order` names (int32 GPU tensor, es_select's);
+        parent_of: the parent slots of ALL pairs of the generation (host ints). The tables swap."""
+        po = self._host_i32(parent_of, len(parent_of), 'parent_of')
+        assert order.dtype == torch.int32 and order.is_contiguous()
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_es_advance(self.h, ctypes.c_uint64(generation), ctypes.c_float(sigma),
+                                           po.ctypes.data_as(ctypes.c_void_p), int(po.size), _ptr(order),
+                                           int(order.numel()), int(n_front), self._stream()), self.h, 'es_advance')
+
+    def es_set_elite(self, elite_slot, slot, table='parents'):
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_es_set_elite(self.h, int(elite_slot), self.ES_TABLES[table], int(slot), self._stream()),
+                  self.h, 'es_set_elite')
+
+    def es_load_theta(self, slot, table='parents'):
+        """The handle's theta <- a parent or elite row (device copy): Split.evaluate / evaluate_theta then score it."""
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_es_load_theta(self.h, self.ES_TABLES[table], int(slot), self._stream()), self.h,
+                  'es_load_theta')
+
     # ---------------------------------------------------------------- multi-GPU (RCCL) ----------
     @staticmethod
     def comm_unique_id():

@@ -20,6 +20,7 @@ import msgpack
 import numpy as np
 
 from .nes import NESResult, NESTask
+from .es import ESResult, ESTask
 
 EXP_KEY = 'nic:exp'
 TASK_ID_KEY = 'nic:task_id'
@@ -30,6 +31,7 @@ ARCHIVE_KEY = 'nic:archive'
 MEMBER_KEY = 'nic:member_counter'       # new: per-task member-id allocator (members are noise indices)
 
 _EXT_NDARRAY, _EXT_TASK, _EXT_RESULT, _EXT_TUPLE = 1, 2, 3, 4
+_EXT_ES_TASK, _EXT_ES_RESULT = 5, 6
 
 
 # ---------------------------------------------------------------- codec ---------------------------
@@ -38,6 +40,10 @@ def _default(obj):
         return msgpack.ExtType(_EXT_TASK, serialize(list(obj)))
     if isinstance(obj, NESResult):
         return msgpack.ExtType(_EXT_RESULT, serialize(list(obj)))
+    if isinstance(obj, ESTask):
+        return msgpack.ExtType(_EXT_ES_TASK, serialize(list(obj)))
+    if isinstance(obj, ESResult):
+        return msgpack.ExtType(_EXT_ES_RESULT, serialize(list(obj)))
     if isinstance(obj, tuple):
         return msgpack.ExtType(_EXT_TUPLE, serialize(list(obj)))
     if isinstance(obj, np.ndarray):
@@ -63,6 +69,10 @@ def _ext_hook(code, data):
         return NESTask(*deserialize(data))
     if code == _EXT_RESULT:
         return NESResult(*deserialize(data))
+    if code == _EXT_ES_TASK:
+        return ESTask(*deserialize(data))
+    if code == _EXT_ES_RESULT:
+        return ESResult(*deserialize(data))
     if code == _EXT_TUPLE:
         return tuple(deserialize(data))
     raise ValueError('unknown extension type %d' % code)
