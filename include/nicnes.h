@@ -453,12 +453,35 @@ int nicnes_es_row_stats(nicnes_handle* h, int32_t table, int32_t slot, float* me
  * (src/algorithm/nic_es/nic_es_worker.py) for a slice of the offspring. parent_of_host [count] (HOST, copied): the
  * parent slot of each pair of the slice; member_batch_host as in nicnes_evaluate_batches (nullable); fitness_out
  * [count, 2] fp64 = the fitness of offspring (2k, 2k + 1); seq_out [count, 2, B, seq_length] int32 and logprob_out
- * likewise fp32, both nullable. Always the fused decode (128-row slabs, one workgroup per pair and slab): a shape forced
- * by nicnes_set_decode_split other than (1, 4), and the sampled fitness modes, are NICNES_ERR_UNSUPPORTED. Screening
- * follows nicnes_set_decode_screen as in nicnes_evaluate. Only enqueues. */
+ * likewise fp32, both nullable. The fused decode (128-row slabs, one workgroup per pair and slab) unless
+ * nicnes_set_decode_es says otherwise: a shape forced by nicnes_set_decode_split other than (1, 4), and the sampled
+ * fitness modes, are NICNES_ERR_UNSUPPORTED. Screening follows nicnes_set_decode_screen as in nicnes_evaluate, on the
+ * fused path only. Only enqueues. */
 int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin, int32_t count, float sigma,
                        const int32_t* parent_of_host, const int32_t* member_batch_host, double* fitness_out,
                        int32_t* seq_out, float* logprob_out, void* stream);
+/* The decode path of nicnes_es_evaluate (not a reference interface: ESWorker.fitness decodes one offspring per CPU
+ * process, nic_es_worker.py). mode 0 (the default): always the fused decode. mode 1: automatic, the coop path (the split
+ * shape of 128-row slabs in one persistent launch, nicnes_set_decode_coop) where the handle's own shape rule
+ * (nicnes_decode_shape) picks G = 4 with S = 2 or 4 for (B, count) and the grid fits the GPU at once, as for a rank's
+ * share of a generation (62-63 pairs of mscoco_es.json's 500 at 8 ranks); otherwise fused, never the split path or
+ * 64-row slabs. mode 2: the coop path with the given S (2 or 4; S is 0 in the other modes): an evaluate whose count x
+ * slabs x S workgroups exceed occupancy x CUs, or issued while nicnes_set_decode_coop(h, 0) holds, fails with
+ * NICNES_ERR_INVALID before anything is enqueued. Grows the partial-state scratch as nicnes_set_decode_split does
+ * (synchronising then). Tokens and greedy fitness do not depend on the path; the coop path never screens. */
+int nicnes_set_decode_es(nicnes_handle* h, int32_t mode, int32_t S);
+/* The path an ES evaluate of `count` pairs of a B-image batch would take under the current mode: 0 fused, 2 coop (the
+ * counterpart of nicnes_decode_path; needs no batch, decodes nothing). Fails as that evaluate would under mode 2. */
+int nicnes_decode_path_es(nicnes_handle* h, int32_t B, int32_t count, int32_t* out_host);
+/* The gather of a generation's fitness over the ranks of the bound communicator: replaces ESMaster.run_master collecting
+ * the workers' ESResults (nic_es_master.py:92-113). The ranks evaluate the balanced shards of nicnes_math.h nn_es_shard
+ * (the first n_pairs % ranks ranks hold n_pairs / ranks + 1 pairs, the rest n_pairs / ranks; contiguous, in rank order).
+ * fit_local [count_local, 2] fp64 (device), this rank's shard; fit_all [n_pairs, 2] fp64 (device) in pair order on every
+ * rank: the shards are padded to the largest share in the handle's scratch, gathered with one ncclAllGather and
+ * compacted on the device. NICNES_ERR_INVALID when count_local is not this rank's share of n_pairs or n_pairs is
+ * below the rank count. Only enqueues (the scratch is allocated at the first call). Needs nicnes_es_create. */
+int nicnes_allgather_fitness_es(nicnes_handle* h, const double* fit_local, int32_t count_local, int32_t n_pairs,
+                                double* fit_all, void* stream);
 /* One offspring's parameters, fp32(theta_parent +- delta') exactly as the decode forms them: theta32_out [D] fp32
  * (device). sign 0: +, 1: -. What ESWorker writes to its offspring .pth (for tests, the wire and snapshots). */
 int nicnes_es_offspring(nicnes_handle* h, uint64_t generation, int32_t pair, int32_t sign, float sigma, int32_t parent,

@@ -157,6 +157,15 @@ NN_FN uint64_t nn_noise_index(uint64_t seed, uint64_t iteration, uint64_t member
     return (h % n_slots) * NN_NOISE_ALIGN;
 }
 
+/* ---- nic_es over ranks: the balanced split of a generation's n_pairs pairs (n_pairs >= world). The first
+ *      n_pairs % world ranks take n_pairs / world + 1 pairs, the rest n_pairs / world; shards are contiguous and in
+ *      rank order (the reference hands ESTasks to whichever worker is free, nic_es_master.py:68-90). */
+NN_FN void nn_es_shard(int n_pairs, int rank, int world, int* begin, int* count) {
+    const int q = n_pairs / world, r = n_pairs % world;
+    *begin = rank * q + (rank < r ? rank : r);
+    *count = q + (rank < r ? 1 : 0);
+}
+
 /*
  * Dot-product order ("k permutation"). The engine's dense products are fp32 fma chains
  * acc = fmaf(w[k], x[k], acc) started from the bias, visiting k in this order inside each

@@ -106,6 +106,8 @@ extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead
                                     ParentArgs* pa = nullptr);
 // nic_es: the fused greedy decode (G = 4, S = 1, no sampling, no decode-formed delta') of members with their own base
 // theta (ParentArgs); screened when sa has its buffers and the decode is greedy-only with the bounded lse
+// With p->coop (G = 4, S = 2 or 4, coop_ctr set): the coop path's one persistent launch on the *_es entries (counters
+// zeroed first, p->coop_launch and p->test_stall_ms as in nicnes_launch_decode; never screened)
 extern "C" hipError_t nicnes_launch_decode_es(const DecodeParams* p, const ParentArgs* pa, int member_count, int nslabs,
                                               hipStream_t stream, const ScreenArgs* sa = nullptr);
 // mh: nullable (or mode 0): no decode-formed delta'

@@ -1704,56 +1704,7 @@ __device__ __forceinline__ SCtx<G> make_sctx(const DecodeParams& p) {
 template <int G>
 __global__ __launch_bounds__(NTHREADS) void nicnes_decode_img_kernel(DecodeParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const SCtx<G> c = make_sctx<G>(p);
-    const bool fused_path = G == 4 && p.S == 1;
-    if (fused_path) PROF_MARK(80); else PROF_SPLIT(250);
-    const float* fcm = p.fc + (p.member_batch ? (size_t)p.member_batch[c.member] * p.B_img * p.F : 0);
-    const rsrc_t fc_r = make_rsrc(fcm, 4u * (uint32_t)p.B_img * (uint32_t)p.F);
-    const int fr = c.row_valid ? (c.b + c.sgn * p.sign_off) / p.rpi : 0;      // the lane's fc row (its image)
-    const uint32_t lo = 4u * c.lane;
-    const bool mm = G == 4 || c.hf == 0;
-    StageRegs sr;
-    f32x16 accU[4];
-    const int nK = p.F >> 7;
-    const int nb = 4 / (int)gridDim.x, U0 = nb * c.q;
-    const int ntile = nK * nb;
-    auto desc = [&](int n) {
-        TileDesc d;
-        d.w_off = (uint32_t)p.off_img_w; d.ld = p.F; d.row0 = 32 * (U0 + n % nb); d.nvalid = 32; d.k0 = 128 * (n / nb);
-        d.b_off = (uint32_t)p.off_img_b; d.pad_bias = 0.f;
-        return d;
-    };
-    stage_load(c.theta_r, c.noise_r, desc(0), c.tid, sr);
-    stage_store(lds, desc(0), c.tid, sr);
-    __syncthreads();
-    for (int kc = 0; kc < nK; ++kc) {
-        const uint32_t frow = 4u * (uint32_t)(fr * p.F + 128 * kc + 4 * c.hh);
-#pragma unroll
-        for (int U = 0; U < 4; ++U) {
-            if (U < nb) {
-                const int n = kc * nb + U;
-                if (n + 1 < ntile) stage_load(c.theta_r, c.noise_r, desc(n + 1), c.tid, sr);
-                const float* buf = lds + (n & 1) * STAGE_FLOATS;
-                if (mm) {
-                    if (kc == 0) accU[U] = bias_init(buf + 2 * SIGN_FLOATS + 32 * c.sgn, c.hh);
-                    accU[U] = mfma_tile_fc(accU[U], buf + c.sgn * SIGN_FLOATS, fc_r, frow, c.lane);
-                }
-                if (n + 1 < ntile) stage_store(lds + ((n + 1) & 1) * STAGE_FLOATS, desc(n + 1), c.tid, sr);
-                __syncthreads();
-            }
-        }
-    }
-    if (mm) {
-#pragma unroll
-        for (int U = 0; U < 4; ++U)
-            if (U < nb) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) st1(c.scr_r, lo, X_SLOT(16 * (U0 + U) + r), accU[U][r]);
-            }
-        st1(c.scr_r, lo, U_SLOT, 1.0f);
-    }
-    if (c.q == 0 && c.tid == 0) p.alive[c.wg] = 1;
-    if (fused_path) PROF_MARK(81); else PROF_SPLIT(251);
+#include "decode_img_body.inc"
 }
 
 // The same for a mutated member on the fused path (MutHead): delta' of img_embed formed at the stage store. The
@@ -2943,40 +2894,31 @@ __device__ __forceinline__ bool coop_step(const DecodeParams& p, const Ctx& c, i
 template <bool PAIRS, int S>
 __global__ __launch_bounds__(NTHREADS) void nicnes_decode_coop_kernel(DecodeParams p, int nslabs) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int L = blockIdx.x, q = L % S, gi = L / S;
-    Ctx c;
-    c.tid = threadIdx.x;
-    c.lane = c.tid & 63;
-    c.wave = __builtin_amdgcn_readfirstlane(c.tid >> 6);
-    c.sgn = c.wave >> 2;
-    c.grp = c.wave & 3;
-    c.hh = c.lane >> 5;
-    c.member = gi / nslabs;
-    c.slab = gi % nslabs;
-    c.wg = gi;
-    c.b = c.slab * 128 + c.grp * 32 + (c.lane & 31);
-    c.row_valid = row_ok(p, c.b, c.sgn);
-    c.bc = c.row_valid ? c.b : 0;
-    const uint64_t nidx = p.noise_idx[c.member];
-    const uint32_t Dbytes = 4u * (uint32_t)p.D;
-    c.theta_r = make_rsrc(p.theta, Dbytes);
-    c.noise_r = make_rsrc(p.noise + nidx, Dbytes);
-    float* wscr = p.scratch + ((size_t)c.wg * 8 + c.wave) * (SCR_SLOTS * 64);
-    c.scr_r = make_rsrc(wscr, SCR_SLOTS * 64 * 4);
-    uint32_t* ctr = p.coop_ctr + (size_t)gi * COOP_CTR_STRIDE;
-    uint32_t phase = 0;
-    if (p.test_stall_ms && L == 0) {               // test hook: a partner that arrives past the spin bound
-        if (c.tid == 0) {
-            const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-            while (__builtin_amdgcn_s_memrealtime() - t0 < 100000ull * p.test_stall_ms) __builtin_amdgcn_s_sleep(127);
-        }
-        __syncthreads();
-    }
-    Stage64Regs s64;
-    bool pre = false;
-    float hB[64];
-    for (int t = -1; t <= p.T; ++t)
-        if (!coop_step<PAIRS, S>(p, c, q, lds, t, s64, pre, hB, ctr, phase)) break;
+#include "decode_coop_body.inc"
+}
+
+// ---- nic_es on the coop path: the two kernels above with a base theta per member (ParentArgs) ----
+// A workgroup's member is not blockIdx.x in these grids: the img grid is (q, member, slab), the coop grid S x member
+// slabs workgroups with member = (blockIdx.x / S) / nslabs. The delta' rows of SM-PROPORTIONAL arrive as p.noise /
+// p.noise_idx, as on the fused path.
+__device__ __forceinline__ DecodeParams es_params(const DecodeParams& p, const ParentArgs& pa, int member) {
+    DecodeParams q = p;
+    q.theta = pa.parents + (int64_t)pa.parent_of[member] * pa.stride;
+    return q;
+}
+
+__global__ __launch_bounds__(NTHREADS) void nicnes_decode_img_es_kernel(DecodeParams p0, ParentArgs pa) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int G = 4;
+    const DecodeParams p = es_params(p0, pa, (int)blockIdx.y);
+#include "decode_img_body.inc"
+}
+
+template <bool PAIRS, int S>
+__global__ __launch_bounds__(NTHREADS) void nicnes_decode_coop_es_kernel(DecodeParams p0, ParentArgs pa, int nslabs) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const DecodeParams p = es_params(p0, pa, ((int)blockIdx.x / S) / nslabs);
+#include "decode_coop_body.inc"
 }
 
 // ========== fused path for 64-row slabs (G = 2): every step of a workgroup in one launch =========
@@ -3208,6 +3150,11 @@ extern "C" hipError_t nicnes_decode_init() {
         {(const void*)nicnes_decode_steps_es_kernel<true>, LDS64},
         {(const void*)nicnes_decode_steps_es_kernel<false>, LDS64},
         {(const void*)nicnes_decode_steps_screen_es_kernel, LDS_SCREEN},
+        {(const void*)nicnes_decode_img_es_kernel, LDS32},
+        {(const void*)nicnes_decode_coop_es_kernel<true, 2>, LDS64},
+        {(const void*)nicnes_decode_coop_es_kernel<false, 2>, LDS64},
+        {(const void*)nicnes_decode_coop_es_kernel<true, 4>, LDS64},
+        {(const void*)nicnes_decode_coop_es_kernel<false, 4>, LDS64},
         {(const void*)nicnes_decode_logit_kernel<4, true>, LDS64},
         {(const void*)nicnes_decode_logit_kernel<4, false>, LDS64},
         {(const void*)nicnes_decode_logit_kernel<2, true>, LDS64},
@@ -3233,7 +3180,9 @@ extern "C" hipError_t nicnes_decode_init() {
 
 extern "C" hipError_t nicnes_decode_occupancy(int* coop_per_cu, int* sample_per_cu) {
     const void* coop[] = {(const void*)nicnes_decode_coop_kernel<true, 2>, (const void*)nicnes_decode_coop_kernel<false, 2>,
-                          (const void*)nicnes_decode_coop_kernel<true, 4>, (const void*)nicnes_decode_coop_kernel<false, 4>};
+                          (const void*)nicnes_decode_coop_kernel<true, 4>, (const void*)nicnes_decode_coop_kernel<false, 4>,
+                          (const void*)nicnes_decode_coop_es_kernel<true, 2>, (const void*)nicnes_decode_coop_es_kernel<false, 2>,
+                          (const void*)nicnes_decode_coop_es_kernel<true, 4>, (const void*)nicnes_decode_coop_es_kernel<false, 4>};
     int lo = 1 << 30;
     for (const void* f : coop) {
         int n = 0;
@@ -3400,10 +3349,30 @@ extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead*
 
 extern "C" hipError_t nicnes_launch_decode_es(const DecodeParams* p, const ParentArgs* pa, int member_count, int nslabs,
                                               hipStream_t stream, const ScreenArgs* sa) {
-    if (p->G != 4 || p->S != 1 || p->coop || p->sample_u) return hipErrorInvalidValue;
+    if (p->G != 4 || p->sample_u) return hipErrorInvalidValue;
+    if (p->coop ? ((p->S != 2 && p->S != 4) || !p->coop_ctr) : p->S != 1) return hipErrorInvalidValue;
     if (!pa || !pa->parents || !pa->parent_of || pa->stride < p->D) return hipErrorInvalidValue;
     const dim3 block(NTHREADS), grid(member_count, nslabs);
     const bool pairs = p->bounded_lse && p->lp == nullptr;
+    if (p->coop) {      // the coop branch of nicnes_launch_decode on the *_es entries (no screening on this path)
+        hipError_t e = hipMemsetAsync(p->coop_ctr, 0, (size_t)member_count * nslabs * COOP_CTR_STRIDE * sizeof(uint32_t),
+                                      stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(nicnes_decode_img_es_kernel, dim3(p->S, member_count, nslabs), block, LDS32, stream, *p, *pa);
+        const dim3 cgrid(p->S * member_count * nslabs);
+        const void* kf = p->S == 2 ? (pairs ? (const void*)nicnes_decode_coop_es_kernel<true, 2>
+                                            : (const void*)nicnes_decode_coop_es_kernel<false, 2>)
+                                   : (pairs ? (const void*)nicnes_decode_coop_es_kernel<true, 4>
+                                            : (const void*)nicnes_decode_coop_es_kernel<false, 4>);
+        DecodeParams pk = *p;
+        ParentArgs pak = *pa;
+        int ns = nslabs;
+        void* args[] = {&pk, &pak, &ns};
+        e = p->coop_launch ? hipLaunchCooperativeKernel(kf, cgrid, block, args, LDS64, stream)
+                           : hipLaunchKernel(kf, cgrid, block, args, LDS64, stream);
+        if (e != hipSuccess) return e;
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(nicnes_decode_img64_es_kernel, grid, block, LDS64, stream, *p, *pa);
     if (pairs && sa && sa->cap && sa->norm) {
         hipLaunchKernelGGL(nicnes_screen_norm_es_kernel, dim3(member_count), block, 0, stream, *p, *pa, *sa);

@@ -125,6 +125,7 @@ struct nicnes_handle {
     // residency from the same occupancy-bounded grid (coop_fits; MI355X_MICROARCH.md: the cooperative launch adds
     // only the runtime's check of that bound) and costs 0.4 % less per iteration at P = 64 (r04 A/B)
     int coop_launch = 0;
+    int es_dec_mode = 0, es_dec_S = 0; // nicnes_set_decode_es: 0 fused, 1 automatic, 2 coop with es_dec_S
     uint32_t test_stall_ms = 0;       // test hook NICNES_TEST_COOP_STALL (ms): coop workgroup 0 starts late
     int test_stall_left = -1;         // ... on the first NICNES_TEST_COOP_STALL_LAUNCHES coop launches only (-1: all)
     int test_slots = 0;               // test hook NICNES_TEST_SLOTS: this many sampled logit slots (0 = enough)
@@ -197,6 +198,8 @@ struct nicnes_es {
     double* neg = nullptr;            // [2 max_members] select scratch
     float* dbuf = nullptr;            // [max_members, Dp] delta' rows (allocated at the first proportional evaluate)
     uint64_t* didx = nullptr;
+    double* gat = nullptr;            // nicnes_allgather_fitness_es: this rank's padded share | every rank's
+    size_t gat_cap = 0;               // ... in doubles
 };
 
 // A resident evaluation split (nicnes_split_create): N images' fc rows, their references cooked WITHOUT the end token
@@ -264,6 +267,17 @@ void layout(const nicnes_config* c, int64_t* off) {
     off[7] = o; o += 5 * R * R;    // core.h2h.weight
     off[8] = o; o += 5 * R;        // core.h2h.bias
     off[9] = o;
+}
+
+// nicnes_allgather_fitness_es: the ranks' padded shares [world, pad, 2] compacted into pair order [n_pairs, 2]
+__global__ void es_compact_fitness_kernel(const double* padded, double* out, int n_pairs, int world, int pad) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;      // entry i of [n_pairs, 2]
+    if (i >= 2 * n_pairs) return;
+    const int k = i >> 1, q = n_pairs / world, r = n_pairs % world;
+    // pair k belongs to the rank whose nn_es_shard holds it
+    const int rank = k < r * (q + 1) ? k / (q + 1) : r + (k - r * (q + 1)) / q;
+    const int begin = rank * q + (rank < r ? rank : r);
+    out[i] = padded[((size_t)rank * pad + (k - begin)) * 2 + (i & 1)];
 }
 
 // nicnes_es_load_theta: a table row widened into the fp64 master (defined first: the kernel below stays the last of
@@ -385,7 +399,8 @@ int alloc_batch(nicnes_handle* h, int max_batch) {
     const int rw = std::max(8 * nslabs_of((int)MB, 4), 4 * nslabs_of((int)MB, 2));
     h->alive_stride = (int32_t)(MM * (size_t)nslabs_of((int)MB, 2));
     const int ns = std::max(nslabs_of((int)MB, 2), nslabs_of((int)MB, 4));
-    h->part_cap = std::max(auto_part_cap((int)MM, (int)MB, h->n_cu), (int64_t)MM * ns * std::max(h->dec_S, 1));
+    const int es_S = h->es_dec_mode == 2 ? h->es_dec_S : (h->es_dec_mode == 1 ? 4 : 1);   // nicnes_set_decode_es's shapes
+    h->part_cap = std::max(auto_part_cap((int)MM, (int)MB, h->n_cu), (int64_t)MM * ns * std::max({h->dec_S, es_S, 1}));
     int rc = dalloc(h, &h->seq, MM * 2 * MB * T);
     if (!rc) rc = dalloc(h, &h->lp, MM * 2 * MB * T);
     if (!rc) rc = dalloc(h, &h->row_scores, MM * 2 * MB);
@@ -2121,7 +2136,7 @@ int nicnes_es_free(nicnes_handle* h) {
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     void* bufs[] = {es->ptab[0], es->ptab[1], es->etab, es->pmean[0], es->pmean[1], es->pzero[0], es->pzero[1], es->emean,
-                    es->ezero, es->part_sum, es->part_zero, es->parent_of, es->neg, es->dbuf, es->didx};
+                    es->ezero, es->part_sum, es->part_zero, es->parent_of, es->neg, es->dbuf, es->didx, es->gat};
     for (void* q : bufs)
         if (q) (void)hipFree(q);
     delete es;
@@ -2348,6 +2363,108 @@ int nicnes_es_advance(nicnes_handle* h, uint64_t generation, float sigma, const 
     return NICNES_OK;
 }
 
+// The path of an ES evaluate of `count` pairs of a B-image batch under nicnes_set_decode_es: *coop_S = 0 (fused) or the
+// coop path's S. Mode 1 takes the coop path only where the handle's own shape rule picks 128-row slabs with S = 2 or 4
+// and the grid fits (coop_fits, which nicnes_set_decode_coop(h, 0) turns off); it never takes the split path or 64-row
+// slabs. Mode 2 fails, before anything is enqueued, when its grid cannot be resident at once.
+static int es_decode_choice(nicnes_handle* h, int B, int count, int* coop_S) {
+    *coop_S = 0;
+    if (h->es_dec_mode == 0) return NICNES_OK;
+    if (h->es_dec_mode == 1) {
+        int G = 0, nslabs = 0, S = 0;
+        decode_shape(h, B, count, &G, &nslabs, &S);
+        if (G == 4 && (S == 2 || S == 4) && coop_fits(h, G, nslabs, S, count) &&
+            (int64_t)count * nslabs * S <= h->part_cap)
+            *coop_S = S;
+        return NICNES_OK;
+    }
+    const int S = h->es_dec_S, nslabs = nslabs_of(B, 4);
+    const int64_t wgs = (int64_t)count * nslabs * S, bound = (int64_t)h->coop_occ * h->n_cu;
+    if (!h->coop_mode)
+        return fail(h, NICNES_ERR_INVALID, "nic_es coop decode: the coop path is off (nicnes_set_decode_coop(h, 0))");
+    if (wgs > bound)
+        return fail(h, NICNES_ERR_INVALID,
+                    "nic_es coop decode: count x slabs x S = " + std::to_string(wgs) +
+                        " workgroups cannot be resident at once: the bound is occupancy x CUs = " + std::to_string(bound));
+    if (!coop_fits(h, 4, nslabs, S, count))
+        return fail(h, NICNES_ERR_INVALID, "nic_es coop decode: the vocabulary has fewer 64-row stages than S");
+    if (wgs > h->part_cap)
+        return fail(h, NICNES_ERR_INVALID, "nic_es coop decode: beyond the partial-state buffer (nicnes_set_decode_es)");
+    *coop_S = S;
+    return NICNES_OK;
+}
+
+int nicnes_set_decode_es(nicnes_handle* h, int32_t mode, int32_t S) {
+    if (!h) return NICNES_ERR_INVALID;
+    if (mode < 0 || mode > 2) return fail(h, NICNES_ERR_INVALID, "nicnes_set_decode_es: mode 0 fused, 1 automatic, 2 coop");
+    if (mode == 2 ? (S != 2 && S != 4) : S != 0)
+        return fail(h, NICNES_ERR_INVALID, "nicnes_set_decode_es: S is 2 or 4 with mode 2, and 0 otherwise");
+    HIPC(h, hipSetDevice(h->device));
+    if (mode) {                        // the partial states of the widest coop shape asked for, as nicnes_set_decode_split
+        const int64_t need = (int64_t)h->cfg.max_members * nslabs_of(h->cfg.max_batch, 4) * (mode == 2 ? S : 4);
+        if (need > h->part_cap) {
+            float* np = nullptr;
+            int rc = dalloc(h, &np, (size_t)need * PART_FLOATS);
+            if (rc) return rc;
+            HIPC(h, hipDeviceSynchronize());
+            (void)hipFree(h->part);
+            h->part = np;
+            h->part_cap = need;
+        }
+    }
+    h->es_dec_mode = mode;
+    h->es_dec_S = S;
+    return NICNES_OK;
+}
+
+int nicnes_decode_path_es(nicnes_handle* h, int32_t B, int32_t count, int32_t* out_host) {
+    if (!h || !out_host || B < 1 || count < 1) return NICNES_ERR_INVALID;
+    int coop_S = 0;
+    if (int rc = es_decode_choice(h, B, count, &coop_S)) return rc;
+    *out_host = coop_S ? 2 : 0;
+    return NICNES_OK;
+}
+
+int nicnes_allgather_fitness_es(nicnes_handle* h, const double* fit_local, int32_t count_local, int32_t n_pairs,
+                                double* fit_all, void* stream) {
+    ES_STATE(h);
+    if (!fit_local || !fit_all || count_local < 1 || n_pairs < 1) return NICNES_ERR_INVALID;
+    if (!h->comm) return fail(h, NICNES_ERR_INVALID, "no communicator (nicnes_comm_init / nicnes_comm_attach)");
+    int world = 1, rank = 0;
+    NCCLC(h, ncclCommCount(h->comm, &world));
+    NCCLC(h, ncclCommUserRank(h->comm, &rank));
+    if (n_pairs < world) return fail(h, NICNES_ERR_INVALID, "nicnes_allgather_fitness_es: fewer pairs than ranks");
+    int begin = 0, share = 0;
+    nn_es_shard(n_pairs, rank, world, &begin, &share);
+    if (count_local != share)
+        return fail(h, NICNES_ERR_INVALID, "nicnes_allgather_fitness_es: count_local is not this rank's share of n_pairs (" +
+                                               std::to_string(share) + ")");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    const int pad = (n_pairs + world - 1) / world;             // the largest share: every rank sends this many pairs
+    const size_t need = (size_t)(world + 1) * pad * 2;
+    if (need > es->gat_cap) {                                  // (grown at the first gather of a larger generation)
+        double* np = nullptr;
+        int rc = dalloc(h, &np, need);
+        if (rc) return rc;
+        if (es->gat) {
+            HIPC(h, hipDeviceSynchronize());
+            (void)hipFree(es->gat);
+        }
+        es->gat = np;
+        es->gat_cap = need;
+    }
+    double* send = es->gat;
+    double* recv = es->gat + (size_t)pad * 2;
+    HIPC(h, hipMemsetAsync(send, 0, (size_t)pad * 2 * sizeof(double), s));
+    HIPC(h, hipMemcpyAsync(send, fit_local, (size_t)share * 2 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    NCCLC(h, ncclAllGather(send, recv, (size_t)pad * 2, ncclDouble, h->comm, s));
+    hipLaunchKernelGGL(es_compact_fitness_kernel, dim3((unsigned)((2 * n_pairs + 255) / 256)), dim3(256), 0, s, recv, fit_all,
+                       n_pairs, world, pad);
+    HIPC(h, hipGetLastError());
+    return NICNES_OK;
+}
+
 int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin, int32_t count, float sigma,
                        const int32_t* parent_of_host, const int32_t* member_batch_host, double* fitness_out,
                        int32_t* seq_out, float* logprob_out, void* stream) {
@@ -2362,6 +2479,8 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
     if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
     if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
     if (es->n_parents < 1) return fail(h, NICNES_ERR_INVALID, "nicnes_es_set_parent_count first");
+    int coop_S = 0;                    // 0: the fused path; 2 or 4: the coop path (nicnes_set_decode_es)
+    if (int rc = es_decode_choice(h, h->B, count, &coop_S)) return rc;
     hipStream_t s = (hipStream_t)stream;
     HIPC(h, hipSetDevice(h->device));
     const int32_t* mb = nullptr;
@@ -2423,13 +2542,18 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
     const int rows = h->B, nslabs = nslabs_of(rows, 4);
     ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr};
     const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)count * nslabs >= h->n_cu);
-    if (screen_on && !p.lp && bounded && h->screen_cap && h->screen_norm && (int64_t)count * nslabs <= h->screen_wgs) {
+    if (!coop_S && screen_on && !p.lp && bounded && h->screen_cap && h->screen_norm &&
+        (int64_t)count * nslabs <= h->screen_wgs) {         // screening is a property of the fused path
         sa.cap = h->screen_cap;
         sa.norm = h->screen_norm;
     }
     p.G = 4;
-    p.S = 1;
+    p.S = coop_S ? coop_S : 1;
     p.part = h->part;
+    p.coop = coop_S ? 1 : 0;
+    p.coop_launch = h->coop_launch;
+    p.test_stall_ms = h->test_stall_left != 0 ? h->test_stall_ms : 0;
+    if (p.coop && h->test_stall_ms && h->test_stall_left > 0) --h->test_stall_left;
     p.no_exit = (p.lp && nslabs > 1) ? 1 : 0;
     p.coop_ctr = h->coop_ctr;
     p.alive2 = h->alive + h->alive_stride;
@@ -2456,7 +2580,8 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
     if (h->timing) HIPC(h, hipEventRecord(h->ev[0], s));
     ParentArgs pa{es->ptab[es->cur], es->parent_of, es->Dp};
     // the pairs in parts on the engine's streams when nicnes_set_decode_streams asks for it (as launch_decode_parts)
-    const int nstr = std::min(count, std::max(h->dec_streams, 1));
+    // (the coop launch needs all its workgroups resident: never split over streams)
+    const int nstr = p.coop ? 1 : std::min(count, std::max(h->dec_streams, 1));
     if (nstr > 1) {
         if (!h->ev_fork) HIPC(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
         for (int i = 0; i < nstr - 1; ++i)

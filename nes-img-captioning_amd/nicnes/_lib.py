@@ -30,7 +30,7 @@ EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_create', 'nicne
            'nicnes_es_create', 'nicnes_es_free', 'nicnes_es_set_mutation', 'nicnes_es_set_parent',
            'nicnes_es_set_parent_count', 'nicnes_es_get_row', 'nicnes_es_row_stats', 'nicnes_es_evaluate',
            'nicnes_es_offspring', 'nicnes_es_select', 'nicnes_es_advance', 'nicnes_es_set_elite',
-           'nicnes_es_load_theta']
+           'nicnes_es_load_theta', 'nicnes_set_decode_es', 'nicnes_decode_path_es', 'nicnes_allgather_fitness_es']
 
 
 class NicnesConfig(ctypes.Structure):
@@ -130,6 +130,9 @@ def lib(path=None):
         'nicnes_es_advance': (c.c_int, [vp, u64, f32, vp, i32, vp, i32, i32, vp]),
         'nicnes_es_set_elite': (c.c_int, [vp, i32, i32, i32, vp]),
         'nicnes_es_load_theta': (c.c_int, [vp, i32, i32, vp]),
+        'nicnes_set_decode_es': (c.c_int, [vp, i32, i32]),
+        'nicnes_decode_path_es': (c.c_int, [vp, i32, i32, vp]),
+        'nicnes_allgather_fitness_es': (c.c_int, [vp, vp, i32, i32, vp, vp]),
         'nicnes_comm_unique_id': (c.c_int, [vp]),
         'nicnes_comm_init': (c.c_int, [vp, i32, i32, vp]),
         'nicnes_comm_attach': (c.c_int, [vp, vp]),

@@ -570,6 +570,34 @@ class Engine:
         out = (fit,) + ((seq,) if return_seq else ()) + ((lp,) if return_lp else ())
         return out if len(out) > 1 else fit
 
+    ES_DECODE_MODES = {'fused': 0, 'auto': 1, 'coop': 2}
+
+    def es_set_decode(self, mode='fused', S=0):
+        """The decode path of es_evaluate: 'fused' (the default), 'auto' (the coop path where the engine's shape rule
+        picks 128-row slabs with S = 2 or 4 and the grid fits the GPU at once, else fused) or 'coop' with S = 2 or 4 (an
+        evaluate that does not fit raises before anything is enqueued). Tokens do not depend on it."""
+        code = self.ES_DECODE_MODES[mode] if isinstance(mode, str) else int(mode)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_set_decode_es(self.h, code, int(S)), self.h, 'es_set_decode')
+
+    def es_decode_path(self, B=None, count=1):
+        """'fused' or 'coop': the path an es_evaluate of `count` pairs would take under the current es_set_decode."""
+        out = ctypes.c_int32()
+        check(self.L.nicnes_decode_path_es(self.h, int(B or self.B), int(count), ctypes.byref(out)), self.h,
+              'es_decode_path')
+        return ('fused', 'split', 'coop')[out.value]
+
+    def es_allgather_fitness(self, fit_local, n_pairs, fit_all=None):
+        """fit_all [n_pairs, 2] in pair order <- every rank's shard fit_local [count, 2] of nicnes.es.es_shard, over the
+        communicator of comm_init (shards may differ by one pair)."""
+        if fit_all is None:
+            fit_all = torch.empty((int(n_pairs), 2), dtype=torch.float64, device=self.device)
+        assert fit_local.dtype == torch.float64 and fit_local.is_contiguous() and fit_all.is_contiguous()
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_allgather_fitness_es(self.h, _ptr(fit_local), int(fit_local.shape[0]), int(n_pairs),
+                                                     _ptr(fit_all), self._stream()), self.h, 'es_allgather_fitness')
+        return fit_all
+
     def es_offspring(self, generation, pair, sign, sigma, parent):
         """fp32 theta [D] (GPU) of offspring (pair, sign: 0 +, 1 -) of `generation` over parent slot `parent`."""
         out = torch.empty(self.D, dtype=torch.float32, device=self.device)

@@ -5,6 +5,8 @@
   draw_parents         the parent of every offspring pair (ESWorker.fitness, nic_es_worker.py:150-162), counter-based
   Podium               tools/podium.py on scores and slots
   EngineESMaster.run   ESMaster.run_master + ESIteration.record_parents (nic_es_master.py:55-148, nic_es/iteration.py)
+  es_shard             the pairs of a generation a rank evaluates (ESMaster hands ESTasks to whichever worker is free)
+  python -m nicnes.es  a run of an experiment JSON, alone or as one rank of a torchrun world (main)
 
 Where the engine departs from the reference (DESIGN.md, section "nic_es"):
 * The unit is the antithetic pair: pair k of a generation gives offspring 2k = parent + delta' and 2k + 1 = parent -
@@ -14,6 +16,9 @@ Where the engine departs from the reference (DESIGN.md, section "nic_es"):
   the selected offspring are written, on the device (Engine.es_advance).
 * The parents of a generation are drawn by a counter-based hash, then sorted across the pair ids (pairs are
   exchangeable), so members that share a parent launch next to each other.
+* Over several ranks (EngineESMaster(rank=, world_size=)) every rank evaluates its own es_shard of the pairs, the
+  fitness is gathered, and selection, podium, schedule and the advance run replicated on every rank: the parent and
+  elite tables stay identical with no theta ever sent (the reference's workers write every offspring to a shared disk).
 * From zero, population_size host-initialised parents are perturbed; the reference makes generation 1's offspring
   fresh random models (ESIteration.init_from_zero keeps the parents None).
 """
@@ -146,6 +151,36 @@ def draw_parents(seed, generation, n_pairs, n_parents, selection='uniform', tour
     return out
 
 
+def es_shard(n_pairs, rank, world):
+    """(begin, count) of the pairs rank `rank` of `world` evaluates (include/nicnes_math.h nn_es_shard): the first
+    n_pairs % world ranks take n_pairs // world + 1 pairs, the rest n_pairs // world; contiguous, in rank order."""
+    n_pairs, rank, world = int(n_pairs), int(rank), int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError('rank %d of %d ranks' % (rank, world))
+    if n_pairs < world:
+        raise ValueError('%d pairs cannot be split over %d ranks: every rank needs a pair' % (n_pairs, world))
+    q, r = divmod(n_pairs, world)
+    return rank * q + min(rank, r), q + (1 if rank < r else 0)
+
+
+def pad_shard(fit_local, n_pairs, world):
+    """A rank's shard fitness [count, 2] padded with zeros to the largest share [ceil(n_pairs / world), 2]: what an
+    all-gather of equal parts takes."""
+    import torch
+    pad = -(-int(n_pairs) // int(world))
+    out = torch.zeros((pad, 2), dtype=fit_local.dtype, device=fit_local.device)
+    out[:fit_local.shape[0]] = fit_local
+    return out
+
+
+def compact_shards(padded_all, n_pairs, world):
+    """The gathered padded shares [world * pad, 2] -> the generation's fitness [n_pairs, 2] in pair order."""
+    import torch
+    pad = -(-int(n_pairs) // int(world))
+    rows = padded_all.reshape(int(world), pad, 2)
+    return torch.cat([rows[r, :es_shard(n_pairs, r, world)[1]] for r in range(int(world))], 0).contiguous()
+
+
 def tournament_draws(key, n_parents, tournament_size):
     """min(tournament_size, n_parents) distinct parent slots: a partial Fisher-Yates over range(n_parents), draw t
     from splitmix64(key ^ t)."""
@@ -206,12 +241,30 @@ class EngineESMaster:
     """ESMaster.run_master on one engine. Per generation (nic_es_master.py:68-127 and ESIteration.record_parents):
     evaluate the offspring; validate the previous generation's elite candidates; update the podium and the patience /
     schedule curriculum; select population_size - num_elites parents, the first num_elite_cands of them being the next
-    candidates; the new parents are the podium's elites + the selected."""
+    candidates; the new parents are the podium's elites + the selected.
+
+    Over world_size ranks (one engine each) every rank runs the same generations: it evaluates its own es_shard of the
+    pairs, the fitness is gathered (comm=None: torch.distributed on `group`, gloo or nccl; comm='engine': the engine's
+    C-ABI communicator after Engine.comm_init), and everything after the gather is replicated, so every rank ends a
+    generation with the same parents, elites, podium, candidates and schedule. Rank 0 holds the Validator; its scores
+    reach the other ranks in one collective (they pass validator=True and never score). Snapshots are rank 0's.
+    decode: Engine.es_set_decode's mode, or ('coop', S); the default is 'fused' on one rank and 'auto' over several,
+    where a rank's share may no longer fill the GPU with one workgroup per pair and slab."""
 
     def __init__(self, spec, engine, validator=None, log_dir=None, seed=0, thetas=None, from_single=None,
-                 sort_parents=True):
+                 sort_parents=True, rank=0, world_size=1, group=None, comm=None, decode=None):
         from .master import Schedule
         self.spec, self.e, self.validator = spec, engine, validator
+        self.rank, self.world, self.group = int(rank), int(world_size), group
+        if comm not in (None, 'engine'):
+            raise ValueError("comm: None (torch.distributed) or 'engine' (the engine's RCCL communicator)")
+        self.comm = comm
+        self.shard = es_shard(spec.n_pairs, self.rank, self.world)
+        if decode is None:
+            decode = 'fused' if self.world == 1 else 'auto'
+        self.decode = decode
+        if decode != 'fused' or self.world > 1:       # (today's single-rank callers' engines are left untouched)
+            engine.es_set_decode(*((decode,) if isinstance(decode, str) else tuple(decode)))
         self.log_dir = log_dir or spec.config.log_dir or 'logs/nices'
         self.seed = int(seed)
         self.sort_parents = bool(sort_parents)
@@ -263,32 +316,79 @@ class EngineESMaster:
         e = self.e
         scored = []
         if self.validator is not None:
-            for i, slot in enumerate(self.cands):
-                e.es_load_theta(slot)
-                scored.append(('g%dc%d' % (generation, i), float(self.validator.accuracy()), slot))
+            scores = []
+            if self.rank == 0:
+                for slot in self.cands:
+                    e.es_load_theta(slot)
+                    scores.append(float(self.validator.accuracy()))
+            scores = self._share_scores(scores, len(self.cands))
+            scored = [('g%dc%d' % (generation, i), scores[i], slot) for i, slot in enumerate(self.cands)]
         for place, table, src in self.podium.record_elites(scored):
             e.es_set_elite(place, src, table)
         return scored
 
+    def _share_scores(self, scores, n):
+        """Rank 0's validation scores on every rank, in one collective (as EngineMaster._validate shares its score)."""
+        if self.world == 1 or n == 0:
+            return scores
+        import torch
+        t = torch.zeros((n, 2), dtype=torch.float64, device=self.e.device)
+        if self.rank == 0:
+            t[:, 0] = torch.tensor(scores, dtype=torch.float64)
+        if self.comm == 'engine':
+            allv = torch.empty((self.world * n, 2), dtype=torch.float64, device=self.e.device)
+            self.e.allgather_fitness(t, allv)
+            t = allv[:n]
+        else:
+            import torch.distributed as dist
+            t = self._host_if_gloo(t)
+            dist.broadcast(t, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
+        return [float(v) for v in t[:, 0].cpu().numpy()]
+
+    def _host_if_gloo(self, t):
+        """gloo moves host memory: a device tensor goes through the host (the rehearsal of several ranks on one GPU)."""
+        import torch.distributed as dist
+        return t.cpu() if dist.get_backend(self.group) == 'gloo' else t
+
+    def _gather_fitness(self, fit_local):
+        """The generation's fitness [n_pairs, 2] in pair order on every rank, from the ranks' shards (unequal by at most
+        one pair): padded to the largest share, gathered, compacted."""
+        n = self.spec.n_pairs
+        if self.comm == 'engine':          # (also at one rank: the communicator's identity exchange)
+            return self.e.es_allgather_fitness(fit_local, n)
+        if self.world == 1:
+            return fit_local
+        import torch
+        import torch.distributed as dist
+        mine = self._host_if_gloo(pad_shard(fit_local, n, self.world))
+        allp = torch.empty((self.world * mine.shape[0], 2), dtype=mine.dtype, device=mine.device)
+        dist.all_gather_into_tensor(allp, mine, group=self.group)
+        return compact_shards(allp, n, self.world).to(self.e.device)
+
     def step(self, batch):
-        """One generation on `batch` ((fc, gts), or the reference's batch dict). Returns its stats record."""
+        """One generation on `batch` ((fc, gts), or the reference's batch dict), on every rank. Returns its stats
+        record."""
         import torch
         from ._lib import DecodeFault
         from .nes import engine_batch
         e, spec, sc = self.e, self.spec, self.sched
         t0 = time.time()
+        before = dict(sc.__dict__)
         sc.incr_iteration()
         g = sc.iteration
         sigma = sc.noise_stdev
         fc, gts = engine_batch(batch, e) if isinstance(batch, dict) else batch
         e.set_batch(fc, gts)
         parent_of = self.parents_of(g)
-        fit = e.es_evaluate(g, 0, spec.n_pairs, sigma, parent_of)                                    # 1
+        begin, count = self.shard
+        fit = self._gather_fitness(e.es_evaluate(g, begin, count, sigma, parent_of[begin:begin + count]))   # 1
         n_keep = spec.population_size - spec.num_elites
         order = e.es_select(fit, n_keep)                      # 4, enqueued behind the evaluate: no host sync between
         fit_h = fit.cpu().numpy()
-        if np.isnan(fit_h).any():                             # nothing of this generation is recorded
-            raise DecodeFault('generation %d: NaN fitness; the parents, podium and candidates are those before it' % g)
+        if np.isnan(fit_h).any():                             # nothing of this generation is recorded, on any rank
+            sc.__dict__.update(before)
+            raise DecodeFault('generation %d: NaN fitness; the parents, podium, candidates and schedule are those before it'
+                              % g)
         scored = self._validate_candidates(g)                                                        # 2, 3
         sc.record_generation(self.podium.is_bad_generation())
         n_front = len(self.podium.best_elites())
@@ -303,9 +403,9 @@ class EngineESMaster:
                'best_val_score': best[0][1] if best else None, 'step_time': time.time() - t0}
         self.stats.append(rec)
         freq = spec.config.snapshot_freq
-        if freq and g % freq == 0:
+        if self.rank == 0 and freq and g % freq == 0:
             self.save_snapshot()
-        if torch.cuda.is_available():
+        if torch.cuda.is_available() and torch.device(e.device).type == 'cuda':
             torch.cuda.current_stream(e.device).synchronize()
         return rec
 
@@ -351,3 +451,177 @@ class EngineESMaster:
         for i, (_, score) in enumerate(self.podium.best_elites()):
             out['best_elites'].append((save(os.path.join('best', 'best_elite'), '0_%d_elite.pth' % i, i, 'elites'), score))
         return out
+
+
+# ---- python -m nicnes.es: a run of an experiment, alone or as one rank of a torchrun world -----------------------------
+class _RowsLoader:
+    """What nicnes.validation.Validator reads, over given fc rows and their label rows (a synthetic 'val' split)."""
+
+    def __init__(self, fc, gts, T):
+        import types
+        n = fc.shape[0]
+        self._fc, self.seq_length, self.ix_to_word = fc, T, {}
+        self.split_ix = {'val': list(range(n))}
+        self.info = {'images': [{'id': i} for i in range(n)]}
+        counts = np.array([g.shape[0] for g in gts])
+        ends = np.cumsum(counts)
+        self.labels = types.SimpleNamespace(labels=np.concatenate(gts, 0).astype(np.int32),
+                                            label_start_ix=ends - counts + 1, label_end_ix=ends)
+
+    def fc_feature(self, ix):
+        return self._fc[ix]
+
+
+def _synthetic_rows(engine, theta, n, fc_seed, ref_seed, df_sets=0):
+    """n seeded images with references derived from the greedy captions of `theta` (nicnes.synthetic): (fc, gts, df,
+    ref_len_raw). The handle's theta is set to `theta`: a validation may have left another row there, on rank 0 only."""
+    from . import synthetic as S
+    engine.set_theta(theta)
+    fc = S.fc_feats(n, engine.cfg.fc_feat_size, fc_seed)
+    sp = engine.make_split(fc)
+    base = sp.decode().cpu().numpy()
+    sp.close()
+    gts, df, ref_len_raw = S.build_references(base, engine.cfg.vocab_size, ref_seed, 5, max(df_sets, n),
+                                              engine.cfg.seq_length)
+    return fc, gts, df, ref_len_raw
+
+
+def parse_args(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog='python -m nicnes.es', description='nic_es generations of an mscoco_es.json-shaped '
+                                 'experiment on the engine; under torchrun (RANK / LOCAL_RANK / WORLD_SIZE) one rank of a '
+                                 'world that shards every generation over its GPUs')
+    ap.add_argument('experiment', help='experiment JSON (algorithm nic_es)')
+    ap.add_argument('--generations', type=int, default=None, help='default: config.max_nb_iterations')
+    ap.add_argument('--seed', type=int, default=0, help='parent draws, initial parents, noise indices')
+    ap.add_argument('--comm', choices=['torch', 'engine'], default='torch',
+                    help="the fitness exchange: torch.distributed, or the engine's own RCCL communicator")
+    ap.add_argument('--backend', choices=['gloo', 'nccl'], default='nccl', help='torch.distributed backend')
+    ap.add_argument('--share-gpu', action='store_true',
+                    help='every rank on device 0 with the coop decode off (a rehearsal of the ranks on one GPU)')
+    ap.add_argument('--synthetic', action='store_true', help='batches and a validation split from nicnes.synthetic')
+    ap.add_argument('--dump', default=None, metavar='DIR',
+                    help='every rank writes its final parent and elite rows (rank<r>.npz) and podium, schedule and '
+                         'per-generation fitness (rank<r>.json) there')
+    ap.add_argument('--log_dir', default=None)
+    ap.add_argument('--data_root', default='.', help="directory the caption_options paths are relative to")
+    ap.add_argument('--df_path', default=None, help='document-frequency table of the training split (data.load_df_table)')
+    ap.add_argument('--noise_len', type=int, default=1 << 27)
+    ap.add_argument('--decode', default=None, help="fused | auto | coop2 | coop4 (default: fused alone, auto over ranks)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    import json
+    args = parse_args(argv)
+    rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
+    local_rank = int(os.environ.get('LOCAL_RANK', str(rank)))
+    import torch
+    import nicnes
+    from . import synthetic as S
+    from .validation import Validator
+    dev = 0 if args.share_gpu else local_rank
+    torch.cuda.set_device(dev)
+    if world > 1:
+        import torch.distributed as dist
+        # (--comm engine: torch.distributed only carries the communicator id, over gloo)
+        if args.comm == 'engine' or args.backend == 'gloo':
+            dist.init_process_group('gloo', rank=rank, world_size=world)
+        else:
+            dist.init_process_group('nccl', rank=rank, world_size=world, device_id=torch.device('cuda', dev))
+    exp = load_experiment(args.experiment)
+    loader = None
+    if args.synthetic:
+        spec = ESExperimentSpec(exp)
+    else:
+        from . import data
+        loader = data.loader_from_caption_options(exp, int(exp['config'].get('batch_size') or 1), seed=args.seed,
+                                                  root=args.data_root)
+        spec = ESExperimentSpec(exp, vocab_size=loader.vocab_size, seq_length=loader.seq_length)
+    eng = nicnes.Engine(device=dev, **spec.engine_kwargs(noise_len=args.noise_len, noise_seed=args.seed))
+    comm = None
+    if args.share_gpu and world > 1:
+        eng.set_decode_coop(0)          # ranks time-sharing one GPU: the coop decode assumes the whole device
+    if world > 1 and args.comm == 'engine':
+        uid = [nicnes.Engine.comm_unique_id() if rank == 0 else None]
+        dist.broadcast_object_list(uid, src=0)
+        eng.comm_init(world, rank, uid[0])
+        comm = 'engine'
+    eng.set_noise_table(S.noise_table(args.noise_len))
+    num_val = spec.config.num_val_items
+    validator = None
+    if args.synthetic:
+        dims = S.Dims(eng.cfg.vocab_size, eng.cfg.input_encoding_size, eng.cfg.rnn_size, eng.cfg.fc_feat_size,
+                      eng.cfg.seq_length)
+        theta0 = S.init_theta(dims, args.seed)                 # the captions the synthetic references derive from
+        made = {}
+
+        def batches(bs):
+            if bs not in made:
+                made[bs] = _synthetic_rows(eng, theta0, bs, 1234, 4321, df_sets=256)
+            fc, gts, df, n = made[bs]
+            keys, vals = nicnes.df_table_arrays(df)
+            eng.set_df_table(keys, vals, np.log(float(n)))
+            while True:
+                yield fc, gts
+        if num_val:
+            vfc, vgts, _, _ = _synthetic_rows(eng, theta0, int(num_val), 1236, 4322)
+            validator = Validator(eng, _RowsLoader(vfc, vgts, eng.cfg.seq_length), 'val', int(num_val)) if rank == 0 \
+                else True
+    else:
+        from . import data
+        if args.df_path:
+            df, n = data.load_df_table(args.df_path)
+        else:
+            df, n = {}, 1.0
+        keys, vals = nicnes.df_table_arrays(df)
+        eng.set_df_table(keys, vals, np.log(float(n)))
+
+        def batches(bs):
+            while True:
+                yield loader.get_batch('train', batch_size=bs)
+        if num_val is None or num_val:
+            validator = Validator(eng, loader, 'val', 5000 if num_val is None else int(num_val)) if rank == 0 else True
+    decode = {None: None, 'fused': 'fused', 'auto': 'auto', 'coop2': ('coop', 2), 'coop4': ('coop', 4)}[args.decode]
+    m = EngineESMaster(spec, eng, validator=validator, log_dir=args.log_dir, seed=args.seed, rank=rank, world_size=world,
+                       comm=comm, decode=decode)
+    fitness = []
+    limit = args.generations if args.generations is not None else spec.config.max_nb_iterations
+    done = 0
+    while not limit or done < limit:       # EngineESMaster.run, keeping every generation's fitness for --dump
+        for batch in batches(m.sched.batch_size):
+            m.step(batch)
+            fitness.append(m.last['fitness'].tolist())
+            done += 1
+            if (limit and done >= limit) or m.sched.patience_reached or m.sched.schedule_reached:
+                break
+    if args.dump:
+        os.makedirs(args.dump, exist_ok=True)
+        n_el = len(m.podium.best_elites())
+        np.savez(os.path.join(args.dump, 'rank%d.npz' % rank),
+                 parents=np.stack([eng.es_row(i).cpu().numpy() for i in range(m.n_parents)]),
+                 elites=np.stack([eng.es_row(i, 'elites').cpu().numpy() for i in range(n_el)]) if n_el
+                 else np.zeros((0, eng.D), np.float32))
+        with open(os.path.join(args.dump, 'rank%d.json' % rank), 'w') as f:
+            json.dump({'rank': rank, 'world': world, 'shard': list(m.shard), 'decode_path': eng.es_decode_path(
+                           m.sched.batch_size, m.shard[1]) if hasattr(eng, 'es_decode_path') else None,
+                       'podium': m.podium.best_elites(), 'cands': m.cands, 'schedule': m.sched.to_dict(),
+                       'fitness': fitness, 'stats': [{k: v for k, v in r.items() if k != 'step_time'} for r in m.stats]},
+                      f)
+    if rank == 0:
+        print(json.dumps({'generations': done, 'world': world, 'best_val_score': m.stats[-1]['best_val_score'],
+                          'score_mean': m.stats[-1]['score_mean'],
+                          'step_time_s': [round(r['step_time'], 4) for r in m.stats]}), flush=True)
+    if validator not in (None, True):
+        validator.close()
+    if comm == 'engine':
+        eng.comm_destroy()
+    eng.close()
+    if world > 1:
+        dist.destroy_process_group()
+    return 0
+
+
+if __name__ == '__main__':
+    import sys
+    sys.exit(main())
