@@ -57,11 +57,13 @@ def noise_table(n=1 << 27, seed=123):
 
 
 def substituted_refs(base_caption, vocab_size, rng, n_refs=5, T=16, p_sub=0.3):
-    """n_refs zero-padded label rows derived from one caption."""
+    """n_refs zero-padded label rows derived from one caption. Lengths L ~ U[8, T]; a seq_length T below 8 draws them
+    from U[(T + 1) // 2, T] instead (T = 16 and every T >= 8 as before)."""
     base = [int(t) for t in base_caption if t > 0] or [1]
     rows = np.zeros((n_refs, T), np.int32)
+    lo = 8 if T >= 8 else (T + 1) // 2
     for j in range(n_refs):
-        L = int(rng.integers(8, T + 1))
+        L = int(rng.integers(lo, T + 1))
         toks = [base[k % len(base)] for k in range(L)]
         for k in range(L):
             if rng.random() < p_sub:

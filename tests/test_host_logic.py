@@ -39,6 +39,29 @@ def test_build_references_df_counts_documents():
     assert (w[0],) in df
 
 
+def test_build_references_for_a_short_seq_length():
+    """seq_length below 8 (tests/test_gpu_dims.py): label rows [n_refs, T] with lengths in [(T + 1) // 2, T], zero-padded
+    after an end token, ids inside the vocabulary, n-grams no longer than the row; T >= 8 draws from U[8, T] as before."""
+    for T in (1, 3, 7):
+        base = np.tile(np.arange(1, T + 1), (6, 1))
+        base[2] = 0                                       # an empty base caption
+        gts, df, n = S.build_references(base, 7, seed=2, n_refs=5, df_sets=16, T=T)
+        assert n == 16 and len(gts) == 6 and max(len(g) for g in df) == min(4, T)
+        lens = set()
+        for rows in gts:
+            assert rows.shape == (5, T) and rows.dtype == np.int32 and rows.min() >= 0 and rows.max() <= 7
+            for r in rows:
+                nz = np.nonzero(r == 0)[0]
+                L = nz[0] + 1 if len(nz) else T
+                lens.add(int(L))
+                assert np.all(r[:L - 1] > 0) and np.all(r[L:] == 0)
+        assert min(lens) >= (T + 1) // 2 and max(lens) == T
+    for T in (8, 16):                                     # the first length drawn is U[8, T]'s
+        rows = S.substituted_refs(np.arange(1, 17), 50, np.random.Generator(np.random.PCG64(4)), 1, T)
+        L = int(np.random.Generator(np.random.PCG64(4)).integers(8, T + 1))
+        assert np.all(rows[0, :L - 1] > 0) and np.all(rows[0, L:] == 0) and (L == T or rows[0, L - 1] == 0)
+
+
 def test_fc_features_bu_nonnegative():
     assert (S.fc_feats(4, 2048, 1235, bu=True) >= 0).all()
     assert (S.fc_feats(4, 2048, 1234) < 0).any()
