@@ -374,11 +374,23 @@ int nicnes_last_decode_lse(nicnes_handle* h, int32_t* bounded_host);
  * (128-row slabs, one workgroup per member slab, pair-bounded lse, no log-probs, plain mutations) in bf16 and certifies
  * the candidate tokens it leaves with exact fp32 chains; mode 0 the fp32 loop; mode 2 (the default) screens when the
  * decode has at least as many workgroups (members x slabs) as the GPU has CUs, where it is faster. Tokens do not depend on it.
- * env NICNES_SCREEN=0/1/2 sets the initial value; test hook NICNES_SCREEN_EPS_SCALE (>= 1) widens the screening bound. */
+ * env NICNES_SCREEN=0/1/2 sets the initial value; test hook NICNES_SCREEN_EPS_SCALE (>= 1) widens the screening bound.
+ * env NICNES_SCREEN_ROUNDS (1..64, default 2): the round budget R. A lane with more hits than one hit list holds (8 hit
+ * weights, a crowded lane-stage weighs 4) certifies them in further rounds while it holds at most 8 R; above that its
+ * step goes to the fp32 loop. R bounds the weight, not the number of rounds: packing weights of 4 into rounds of 8 can
+ * take a lane one round more than R. 1: no round after the first. */
 int nicnes_set_decode_screen(nicnes_handle* h, int32_t mode);
-/* the screened decodes' counters since create: [0] candidate ids captured, [1] rows that sent their
- * workgroup's step to the fp32 loop */
+/* the screened decodes' counters since create: [0] candidate ids captured, [1] rows the first certify round left
+ * bad (before the certify rounds each sent its workgroup's step to the fp32 loop; nicnes_screen_reasons says what
+ * became of them) */
 int nicnes_screen_stats(nicnes_handle* h, int64_t* out2_host);
+/* why rows were left bad, and what became of them, since create. Of the rows of nicnes_screen_stats' [1]: [0] with a
+ * lane over the hit-list cap, [1] with a record between the inner and outer tie window, [2] with an evicted record in
+ * the window, [3] with a non-finite bound (or NICNES_FORCE_EXACT); a row may have several. [4] rows that later certify
+ * rounds settled, [5] rows that went to the fp32 loop, [6] workgroup steps that ran it. [7 + k], k < 8: over-cap rows
+ * whose fuller lane holds 8 (k + 1) + 1 .. 8 (k + 2) hit weights (k = 7: or more), i.e. needs at least k + 2 rounds.
+ * [15] waves that ran the fp32 loop, of the 8 of each workgroup step of [6] (the others held no bad row and sat it out) */
+int nicnes_screen_reasons(nicnes_handle* h, int64_t* out16_host);
 /* Test entry (no reference counterpart): every vocabulary logit of member `member` of `iteration` at sigma, sign
  * (0: +, 1: -), over 32 given rows of h (h_rows_dev [32, 128] fp32, unit order), computed twice: out_mfma_dev by the
  * 32-row fp32 MFMA tile path of the exact pass, out_chain_dev by the function the screened decode certifies with (one

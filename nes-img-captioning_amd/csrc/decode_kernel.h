@@ -59,8 +59,20 @@ struct ScreenArgs {
     float* norm;                 // [members][4]: max_v |w+_v|^2, max_v |w-_v|^2, max_v |b+_v|, max_v |b-_v| of the
                                  // member's logit rows (nicnes_screen_norm_kernel, before the decode)
     float scale;                 // >= 1, multiplies eps (test hook NICNES_SCREEN_EPS_SCALE)
-    unsigned long long* ctr;     // [0] candidate ids captured, [1] rows that sent their step to the fp32 loop (atomic)
+    unsigned long long* ctr;     // SCREEN_CTR_WORDS counters (atomic): [0] candidate ids captured, [1] rows the first
+                                 // certify round left bad; of those [2] with a lane over the cap, [3] with a record
+                                 // between the tie windows, [4] with an evicted record in the window, [5] with a
+                                 // non-finite bound (or force_exact); [6] rows of [1] that later rounds settled, [7] rows
+                                 // that went to the fp32 loop, [8] workgroup steps that ran it; [9 + k] over-cap rows
+                                 // whose fuller lane holds 8 (k + 1) + 1 .. 8 (k + 2) hit weights (k = 7: or more);
+                                 // [17] waves that ran the fp32 loop (of the 8 of each workgroup step of [8])
+    int32_t rounds;              // round budget R: a lane may hold up to 8 R hit weights and still be certified in
+                                 // rounds (NICNES_SCREEN_ROUNDS; 1: none after the first). It bounds the weight, not
+                                 // the count: packing crowded hits (weight 4) can take a lane one round more than R
 };
+#define SCREEN_CTR_WORDS 18
+#define SCREEN_ROUNDS_DEFAULT 2
+#define SCREEN_ROUNDS_MAX 64
 
 // A mutated decode on the fused greedy path (mode != 0; the kernels' second argument, so the other kernels' argument
 // layout is untouched): the delta' rows in DecodeParams::noise hold only the parameters from off_log_w on (logit, i2h,

@@ -376,6 +376,26 @@ __device__ __forceinline__ void stage64_store_o(float* buf, int valid, const Lan
     }
 }
 
+// stage64_store_o for a loop only some waves take part in (logit_stages GATED): the tile of a sign none of whose waves
+// does (bit s of `signs` clear) is not written; the biases are
+__device__ __forceinline__ void stage64_store_g(float* buf, int valid, const LaneOffs& o, bool bias,
+                                                const Stage64Regs& r, int signs) {
+    float* b = buf + o.so;
+    if (signs & 1) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) *reinterpret_cast<f32x4*>(b + 16 * u * LDS_ROW) = r.w[u] + r.z[u];
+    }
+    if (signs & 2) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) *reinterpret_cast<f32x4*>(b + (64 + 16 * u) * LDS_ROW) = r.w[u] - r.z[u];
+    }
+    if (bias) {
+        const float delta = r.bz;
+        const float v = o.bslot >= 64 ? r.bw - delta : r.bw + delta;
+        buf[2 * 64 * LDS_ROW + o.bslot] = (o.bslot & 63) < valid ? v : NEG_INF;
+    }
+}
+
 // two independent accumulator chains (stage rows 0-31 and 32-63) over the same B
 __device__ __forceinline__ void mfma_stage64(const float* w, const float* bias, const float (&Bop)[64], int lane,
                                              f32x16& acc0, f32x16& acc1) {
@@ -1124,11 +1144,12 @@ __device__ __forceinline__ void sample_pick(const DecodeParams& p, rsrc_t lr, ui
 // maximum within `delta` of it, delta >= 2 eps + hu_out). After the loop screen_scan lists the lane's words that reach
 // the final threshold, and certify_tiles, each wave over the ids behind its own lanes' lists (the pair behind a hit, or
 // all 32 ids of a crowded lane-stage), computes their exact logits on fp32 MFMA tiles (logit_chain's arithmetic bit for
-// bit); each lane takes its own in id order into the same records the fp32 loop keeps. A step the records cannot
-// decide is run again by the fp32 loop itself (step_body).
+// bit); each lane takes its own in id order into the same records the fp32 loop keeps. A lane with more hits than its
+// list holds certifies them in further rounds (ScreenArgs::rounds). A step the records cannot decide is run again by
+// the fp32 loop itself, on the waves that hold such a row (step_body).
 #define SCREEN_PACK_REL 1.52587890625e-05f   // 2^-16: the word is within 2^-18 |q| of the pair maximum it encodes
 #define SCREEN_HU_MAX 1.9073486328125e-06f   // 2^-19: tie_window's hu_out while lse < 64
-#define SCREEN_HIT_CAP 8                     // hit lane-stages one lane certifies (a crowded one counts 4); more: the fp32 loop
+#define SCREEN_HIT_CAP 8                     // hit lane-stages one lane lists per certify round (a crowded one counts 4)
 struct ScreenStage {
     static constexpr bool replaces = true;
     static constexpr bool bf = true;
@@ -1225,14 +1246,18 @@ __device__ __forceinline__ float logit_chain(const DecodeParams& p, rsrc_t theta
 
 // Pass 1 of the certify: the lane's words against thr (already lowered by the packing error); its hit lane-stages, in
 // stage order, go into its private list in LDS (free between the logit loop's last barrier and the token phase's):
-// entry = stage << 8 | crowded << 4 | pair. cnt: the entries listed; ncand counts the candidate ids captured. Returns
-// false when the lane would certify more than SCREEN_HIT_CAP lane-stages (the step goes to the fp32 loop).
-__device__ __forceinline__ bool screen_scan(rsrc_t cap, uint32_t vo, int nst, float thr, float* lds, int tid, int& cnt,
-                                            int& ncand) {
+// entry = stage << 8 | crowded << 4 | pair. One call lists the hits from stage `from` on while their weights (a crowded
+// one counts 4) sum to at most SCREEN_HIT_CAP: cnt entries; next = the stage of the first hit left out (nst: none, the
+// lane is done), where the lane's next certify round resumes. The first call (first: from = 0) walks every word and
+// also counts the lane's hit weights (hits; next < nst exactly when hits > SCREEN_HIT_CAP: the lane is over the cap)
+// and the candidate ids captured (ncand); a later one stops at the first hit it leaves out.
+__device__ __forceinline__ void screen_scan(rsrc_t cap, uint32_t vo, int nst, float thr, float* lds, int tid, bool first,
+                                            int from, int& cnt, int& next, int& hits, int& ncand) {
     uint32_t* list = reinterpret_cast<uint32_t*>(lds) + tid * SCREEN_HIT_CAP;
-    int hits = 0;
+    int wsum = 0;
     cnt = 0;
-    for (int s0 = 0; s0 < nst; s0 += 16) {
+    next = nst;
+    for (int s0 = from; s0 < nst && (first || next == nst); s0 += 16) {
         uint32_t wd[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j)
@@ -1241,14 +1266,22 @@ __device__ __forceinline__ bool screen_scan(rsrc_t cap, uint32_t vo, int nst, fl
         for (int j = 0; j < 16; ++j) {
             const uint32_t word = wd[j];
             if (s0 + j < nst && __builtin_bit_cast(float, word & ~31u) >= thr) {
-                hits += (word & 16u) ? 4 : 1;
-                ncand += (word & 16u) ? 32 : 2;           // candidate ids captured (certified below unless over the cap)
-                if (cnt < SCREEN_HIT_CAP) list[cnt] = ((uint32_t)(s0 + j) << 8) | (word & 31u);
-                ++cnt;
+                const int wt = (word & 16u) ? 4 : 1;
+                if (first) {
+                    hits += wt;
+                    ncand += (word & 16u) ? 32 : 2;       // candidate ids captured (certified unless the step is over the budget)
+                }
+                if (next == nst) {
+                    if (wsum + wt <= SCREEN_HIT_CAP) {
+                        list[cnt++] = ((uint32_t)(s0 + j) << 8) | (word & 31u);
+                        wsum += wt;
+                    } else {
+                        next = s0 + j;
+                    }
+                }
             }
         }
     }
-    return hits <= SCREEN_HIT_CAP;
 }
 
 // the ids behind a lane's listed hits (the pair, or all 32 of a crowded lane-stage), in increasing order
@@ -1284,7 +1317,7 @@ struct ListItems {
 // k block: the loads of block T + 2 (the next tile's from T = 2 on) are issued before block T's MFMAs, and a block's
 // columns of the tile are overwritten only after the previous tile's MFMAs of that block have read them. Nothing but
 // the wave's own LDS traffic has to be ordered inside the loops: one workgroup barrier in front (the stage buffers the
-// tiles lie over are read until then), none after it.
+// tiles lie over are read until then; SYNC = false: the caller's), none after it.
 // each(f) calls f(id) for the thread's n_mine items in order; sink(L, id) receives them in the same order.
 // LDS (floats): the lists | per wave: tile (SIGN_FLOATS) | 32 biases | CERT_ITEMS item / result words. pm: DECODE_PROF
 // slots of the step (CERT_PROF_AT(t) + 1; < 0: none), wave 0's: lists built, first tile staged, all tiles done.
@@ -1340,7 +1373,7 @@ __device__ __forceinline__ void cert_store(float* tile, int sgn, int T, const Ce
         *reinterpret_cast<f32x4*>(b + 8 * u * LDS_ROW) = sgn ? r.w[u] - r.z[u] : r.w[u] + r.z[u];
 }
 
-template <class Each, class Sink>
+template <bool SYNC = true, class Each, class Sink>
 __device__ __forceinline__ void certify_tiles(const DecodeParams& p, rsrc_t theta_r, rsrc_t noise_r, int sgn,
                                               const float (&hB)[64], float* lds, int tid, int n_mine, const Each& each,
                                               Sink&& sink, int pm) {
@@ -1356,7 +1389,8 @@ __device__ __forceinline__ void certify_tiles(const DecodeParams& p, rsrc_t thet
         inc += lane >= d ? u : 0;
     }
     const int total = __builtin_amdgcn_readlane(inc, 63), first = inc - n_mine;
-    __syncthreads();                                         // the logit loop's last reads of the stage buffers are done
+    // the logit loop's last reads of the stage buffers are done (!SYNC: the caller has had a workgroup barrier since)
+    if constexpr (SYNC) __syncthreads();
 #if DECODE_PROF
     if (pm >= 0 && total == 0 && lane == 0)
         p.seq[(size_t)(blockIdx.x * gridDim.y + blockIdx.y) * 4096 + CERT_PROF_WAVE_AT((pm - 1 - 640) / 5 - 1) + wave] = 0;
@@ -1461,11 +1495,17 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_screen_norm_es_kernel(DecodeP
 
 // Measured and not kept (git history, r04): per-wave LDS progress words in place of the per-stage barrier (+0.4 %),
 // a chain-a-only last stage for the coop ranges (+1.3 % / +2.2 % at P = 64 / 128, or spills inside the loop).
-template <int G, bool PAIRS, bool PEEL = true, class Tail = NoTail, class Hook = NoHook>
+// GATED (the screened decode's fallback, G = 4 and the fp32 stages only): the loop of a workgroup of which only the
+// waves with gact hold a row that needs it. The others still load and store their share of every stage and meet every
+// barrier, in a loop of their own with no MFMA and no epilogue (their st is left alone); the tile of a sign with no
+// such wave (bit of gsgn clear) is not written. A wave with gact runs the ungated loop's code on the same tile: its
+// rows' results depend on its own chains and its sign's tile only.
+template <int G, bool PAIRS, bool PEEL = true, class Tail = NoTail, class Hook = NoHook, bool GATED = false>
 __device__ __forceinline__ void logit_stages(float* lds, const DecodeParams& p, uint64_t nidx, int wave, int sgn,
                                              int hf, const float (&hB)[64], int s0, int s1, RowState& st,
                                              Stage64Regs& s64, bool preloaded = false, Tail&& tail = Tail(),
-                                             const Hook& hook = Hook()) {
+                                             const Hook& hook = Hook(), bool gact = true, int gsgn = 3) {
+    static_assert(!GATED || (G == 4 && !Hook::bf), "the gated loop is the fp32 64-row loop");
     const rsrc_t lw_r = make_rsrc(p.theta + p.off_log_w, 4u * 128u * (uint32_t)p.V1);
     const rsrc_t lz_r = make_rsrc(p.noise + nidx + p.off_log_w, 4u * 128u * (uint32_t)p.V1);
     const rsrc_t lbw_r = make_rsrc(p.theta + p.off_log_b, 4u * (uint32_t)p.V1);
@@ -1486,6 +1526,7 @@ __device__ __forceinline__ void logit_stages(float* lds, const DecodeParams& p, 
     if (!preloaded) stage64_load_o(lsrc(s0), lo, bias, s64);
     auto sstore = [&](float* buf, int valid) __attribute__((always_inline)) {
         if constexpr (Hook::bf) stage64_store_bf(buf, valid, lo, lob.sob, bias, s64);
+        else if constexpr (GATED) stage64_store_g(buf, valid, lo, bias, s64, gsgn);
         else stage64_store_o(buf, valid, lo, bias, s64);
     };
     sstore(lds, lsrc(s0).valid);
@@ -1495,6 +1536,22 @@ __device__ __forceinline__ void logit_stages(float* lds, const DecodeParams& p, 
     if (PEEL) stage64_load_o(lsrc(min(s0 + 1, s1 - 1)), lo, bias, s64);   // (unconditional: one definition of s64)
     else if (s0 + 1 < s1) stage64_load_o(lsrc(s0 + 1), lo, bias, s64);
     __syncthreads();
+    if constexpr (GATED) {
+        // a wave that sits the loop out: its share of stage s + 1 stored and of s + 2 loaded at every stage s, one
+        // barrier per stage, as the waves below do (which run the ungated loop's own code)
+        if (!gact) {
+            for (int s = s0; s < s1; ++s) {
+                if (s + 1 < s1) {
+                    sstore(lds + ((s - s0 + 1) & 1) * STAGE64_FLOATS, lsrc(s + 1).valid);
+                    if (s + 2 < s1) stage64_load_o(lsrc(s + 2), lo, bias, s64);
+                } else {
+                    tail();
+                }
+                __syncthreads();
+            }
+            return;
+        }
+    }
     f32x16 a0, a1, b0, b1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { b0[r] = NEG_INF; b1[r] = NEG_INF; }
@@ -1871,7 +1928,9 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
         float stot = st.s * __builtin_amdgcn_exp2f((st.m - m) * LOG2E) + s_o * __builtin_amdgcn_exp2f((m_o - m) * LOG2E);
         // SCREEN: m and stot are over screened logits, each within eps of its exact one: lse moves by at most 2 eps
         TieWindow w = tie_window(stot, PAIRS, SCREEN ? p.lse_margin + 2.0f * seps : p.lse_margin);
-        bool sforce = false;                     // SCREEN: this step of the workgroup is decided by the fp32 loop
+        bool sforce = false;                     // SCREEN: this step of the workgroup runs the fp32 loop
+        bool sact = true;                        // SCREEN: this wave takes part in it (holds a row the records left bad)
+        int stok = 0x7fffffff;                   // SCREEN: the token the certified records give the row
         float lse = w.lse;
         int tok = 0x7fffffff;
         float lp_tok = 0.f;                      // seq_logprobs: -lse (the max, greedy) or the draw's log-prob
@@ -1902,23 +1961,46 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
                 const float d = 2.0f * seps + w.hu_out;
                 const float thr = (m - d) - SCREEN_PACK_REL * (fabsf(m) + d);
                 const bool need = unf_prev != 0.f || p.no_mask;
-                bool bad = p.force_exact || !(fabsf(thr) < 3.0e38f) || !(w.hu_out <= SCREEN_HU_MAX) || !(stot > 0.f);
+                // pre: the row's bound is unusable (or the test hook asks for the fp32 loop)
+                const bool pre = p.force_exact || !(fabsf(thr) < 3.0e38f) || !(w.hu_out <= SCREEN_HU_MAX) || !(stot > 0.f);
                 st.r1v = st.r0v = st.ev = NEG_INF;
                 st.r1i = st.r0i = 0x7fffffff;
-                int ncand = 0, ccnt = 0;
-                if (need && !bad) {
-                    bad = !screen_scan(scap_r, 4u * (uint32_t)(c.wave * 64 + lane_fresh()), nl, thr, lds,
-                                       c.wave * 64 + lane_fresh(), ccnt, ncand);
-                    if (bad) ccnt = 0;               // over the cap: nothing of this lane is certified
-                }
-                PROF_MARK(CERT_PROF_AT(t));
-                {
-                    const int ctid = c.wave * 64 + lane_fresh();
+                const int ctid = c.wave * 64 + lane_fresh();
+                const uint32_t cvo = 4u * (uint32_t)ctid;
+                int ncand = 0, hits = 0, nxt = nl;
+                bool over = false, multi = false;
+                // Certify rounds. The first lists every lane's hits up to the cap, certifies them and feeds the records;
+                // a lane over the cap (hits > SCREEN_HIT_CAP) then has hits left, from stage nxt on. Unless some needed
+                // lane of the workgroup is over the round budget (then its over-cap lanes certify nothing and the step
+                // goes to the fp32 loop, as with one round), the workgroup goes on in rounds until no lane has any left:
+                // each lists its lane's next hits into the same list, so the records take the lane's ids in increasing
+                // order over all rounds. The lists are lane-private and the item lists and tiles wave-private, so a round
+                // needs no barrier beyond the one that carries its vote.
+                auto round = [&](int ccnt, int pm) __attribute__((always_inline)) {
                     const ListItems items{reinterpret_cast<const uint32_t*>(lds) + ctid * SCREEN_HIT_CAP, ccnt, c.hh, p.V1};
                     int n_mine = 0;
                     items([&](int) { ++n_mine; });
-                    certify_tiles(p, c.theta_r, c.noise_r, c.sgn, hB, lds, ctid, n_mine, items,
-                                  [&](float L, int v) { record1(st, L, v); }, CERT_PROF_AT(t) + 1);
+                    certify_tiles<false>(p, c.theta_r, c.noise_r, c.sgn, hB, lds, ctid, n_mine, items,
+                                         [&](float L, int v) { record1(st, L, v); }, pm);
+                };
+                {
+                    int ccnt = 0;
+                    if (need && !pre) screen_scan(scap_r, cvo, nl, thr, lds, ctid, true, 0, ccnt, nxt, hits, ncand);
+                    PROF_MARK(CERT_PROF_AT(t));
+                    over = hits > SCREEN_HIT_CAP;
+                    // (this barrier is also the one certify_tiles needs in front)
+                    const int ov = __ockl_wgred_or_i32((over ? 1 : 0) | (hits > SCREEN_HIT_CAP * max(sa->rounds, 1) ? 2 : 0));
+                    multi = ov == 1;
+                    if (over && !multi) { ccnt = 0; nxt = nl; }       // over the budget: nothing of this lane is certified
+                    round(ccnt, CERT_PROF_AT(t) + 1);
+                }
+                // (marked unlikely: without it the register allocator weighs these loops like the sweep's and spills there)
+                if (__builtin_expect(multi, 0)) {
+                    while (__syncthreads_or(nxt < nl ? 1 : 0)) {
+                        int ccnt = 0;
+                        if (nxt < nl) screen_scan(scap_r, cvo, nl, thr, lds, ctid, false, nxt, ccnt, nxt, hits, ncand);
+                        round(ccnt, -1);
+                    }
                 }
                 PROF_MARK(CERT_PROF_AT(t) + 4);
 #pragma unroll
@@ -1926,46 +2008,77 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
                 if (ncand && lane_fresh() == 0) atomicAdd(sa->ctr, (unsigned long long)ncand);   // one atomic per wave and step
                 // The fp32 loop's token rule over the certified records, under this (wider) window: the records inside
                 // the outer window are the fp32 loop's, and a state decided here is decided the same way there. A row
-                // left undecided, over the cap or with a non-finite bound sends the workgroup's step to the fp32 loop.
+                // left undecided, over the round budget or with a non-finite bound sends its wave's step to the fp32 loop.
                 const float mx = fmaxf(st.r1v, __shfl_xor(st.r1v, 32));
                 const float sv[4] = {st.r0v, st.r1v, __shfl_xor(st.r0v, 32), __shfl_xor(st.r1v, 32)};
                 const int si[4] = {st.r0i, st.r1i, __shfl_xor(st.r0i, 32), __shfl_xor(st.r1i, 32)};
-                int stok = 0x7fffffff;
-                bool und = win_state(st.ev, mx, w) != 0 || win_state(__shfl_xor(st.ev, 32), mx, w) != 0;
+                const bool evw = win_state(st.ev, mx, w) != 0 || win_state(__shfl_xor(st.ev, 32), mx, w) != 0;
+                bool und2 = false;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int ws = win_state(sv[k], mx, w);
                     if (ws == 1 && si[k] < stok) stok = si[k];
-                    und = und || ws == 2;
+                    und2 = und2 || ws == 2;
                 }
-                const bool bad_o = __shfl_xor((int)bad, 32) != 0;            // the row's other lane half
-                bad = need && (bad || und || bad_o);
-                if (bad && c.hh == 0) atomicAdd(sa->ctr + 1, 1ull);
-                sforce = __syncthreads_or(bad ? 1 : 0) != 0;
-                if (!sforce) {
-                    tok = stok;
-                } else {
-                    row_state_init(st);
-                    logit_stages<4, true>(lds, p, nidx, c.wave, c.sgn, 0, hB, 0, nl, st, s64, false);
+                // the row's two lane halves together. A row neither of whose lanes is over the cap has all its records
+                // after the first round, so bad1 is what one round leaves bad whatever the rounds did since
+                const int hits_o = __shfl_xor(hits, 32);
+                const bool over_r = over || hits_o > SCREEN_HIT_CAP;
+                const bool pre_r = pre || __shfl_xor((int)pre, 32) != 0;
+                const bool bad1 = need && (pre_r || over_r || evw || und2);
+                const bool bad = need && (pre_r || (over_r && !multi) || evw || und2);
+                {
+                    // rows by reason and outcome: one atomic per wave, step and counter that moves
+                    auto rows = [&](bool f, int k) __attribute__((always_inline)) {
+                        const unsigned long long bl = __ballot(f && c.hh == 0);
+                        if (bl && lane_fresh() == 0) atomicAdd(sa->ctr + k, (unsigned long long)__popcll(bl));
+                    };
+                    rows(bad1, 1);
+                    if (__ballot(bad1)) {
+                        rows(bad1 && over_r, 2);
+                        rows(bad1 && und2, 3);
+                        rows(bad1 && evw, 4);
+                        rows(bad1 && pre_r, 5);
+                        rows(bad1 && !bad, 6);
+                        rows(bad, 7);
+                        const int hmax = max(hits, hits_o), hk = min((hmax + SCREEN_HIT_CAP - 1) / SCREEN_HIT_CAP, 9) - 2;
+                        for (int k = 0; k < 8; ++k) rows(need && over_r && hk == k, 9 + k);
+                    }
+                }
+                // the waves that hold a bad row: only they run the fp32 loop's MFMAs and epilogue again
+                const int wbad = __ockl_wgred_or_i32(__ballot(bad) ? 1 << c.wave : 0);
+                sforce = wbad != 0;
+                sact = ((wbad >> c.wave) & 1) != 0;
+                if (sforce && c.tid == 0) atomicAdd(sa->ctr + 8, 1ull);
+                if (sact && lane_fresh() == 0) atomicAdd(sa->ctr + 17, 1ull);     // (sact implies sforce)
+                if (!sact) tok = stok;
+                if (__builtin_expect(sforce, 0)) {       // (unlikely, as above)
+                    const int sgn_on = ((wbad & 0x0f) ? 1 : 0) | ((wbad & 0xf0) ? 2 : 0);
+                    if (sact) row_state_init(st);
+                    logit_stages<4, true, true, NoTail, NoHook, true>(lds, p, nidx, c.wave, c.sgn, 0, hB, 0, nl, st, s64, false,
+                                                                      NoTail(), NoHook(), sact, sgn_on);
                     cell_pre = false;            // s64 now holds logit rows: the cell loads its first tile itself
-                    const float m2 = __shfl_xor(st.m, 32), s2 = __shfl_xor(st.s, 32);
-                    m = fmaxf(st.m, m2);
-                    stot = st.s * __builtin_amdgcn_exp2f((st.m - m) * LOG2E) + s2 * __builtin_amdgcn_exp2f((m2 - m) * LOG2E);
-                    w = tie_window(stot, true, p.lse_margin);
-                    lse = w.lse;
+                    if (sact) {
+                        const float m2 = __shfl_xor(st.m, 32), s2 = __shfl_xor(st.s, 32);
+                        m = fmaxf(st.m, m2);
+                        stot = st.s * __builtin_amdgcn_exp2f((st.m - m) * LOG2E) + s2 * __builtin_amdgcn_exp2f((m2 - m) * LOG2E);
+                        w = tie_window(stot, true, p.lse_margin);
+                        lse = w.lse;
+                    }
                 }
             }
             if (!SCREEN || sforce) {
+            // (SCREEN: a wave that sat the fp32 loop out keeps stok; it only keeps the workgroup's barriers below)
             const float cv[4] = {st.r0v, st.r1v, __shfl_xor(st.r0v, 32), __shfl_xor(st.r1v, 32)};
             const int ci[4] = {st.r0i, st.r1i, __shfl_xor(st.r0i, 32), __shfl_xor(st.r1i, 32)};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int ws = win_state(cv[k], m, w);
-                if (ws == 1 && ci[k] < tok) tok = ci[k];
+                if (ws == 1 && ci[k] < tok && (!SCREEN || sact)) tok = ci[k];
                 amb = amb || ws == 2;
             }
-        const bool ovf = p.force_exact || amb || win_state(st.ev, m, w) != 0 ||
-                         win_state(__shfl_xor(st.ev, 32), m, w) != 0;
+        const bool ovf = (!SCREEN || sact) && (p.force_exact || amb || win_state(st.ev, m, w) != 0 ||
+                                               win_state(__shfl_xor(st.ev, 32), m, w) != 0);
         if (__syncthreads_or(ovf ? 1 : 0)) {
             // rare: more records than tracked fall in the tie window (or, PAIRS mode, the bounds on
             // lse leave a record undecided) -> exact pass. PAIRS: the exp-sum sweep first, then the
@@ -1984,7 +2097,8 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     if (in_window(cv[k], m, lse) && ci[k] < t2) t2 = ci[k];
-                const bool ev2 = p.force_exact || in_window(st.ev, m, lse) || in_window(__shfl_xor(st.ev, 32), m, lse);
+                const bool ev2 = (!SCREEN || sact) &&
+                                 (p.force_exact || in_window(st.ev, m, lse) || in_window(__shfl_xor(st.ev, 32), m, lse));
                 find = __syncthreads_or(ev2 ? 1 : 0) != 0;
                 if (!find) tok = t2;
             }
@@ -1994,6 +2108,7 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
                 tok = min(best, __shfl_xor(best, 32));
             }
             if (c.tid == 0) atomicAdd(p.stats + 0, 1);
+            if (SCREEN && !sact) tok = stok;
         }
             }
         lp_tok = -lse;                           // seq_logprobs[:, t-1] = max lp = fp32((m - m) - lse) (nets.py:208,241)

@@ -156,7 +156,8 @@ struct nicnes_handle {
     uint32_t* screen_cap = nullptr;    // capture slots of screen_wgs workgroups (allocated at the first screened decode)
     int64_t screen_wgs = 0;
     float* screen_norm = nullptr;      // [max_members][4]
-    unsigned long long* screen_ctr = nullptr;   // [2] (ScreenArgs::ctr)
+    unsigned long long* screen_ctr = nullptr;   // [SCREEN_CTR_WORDS] (ScreenArgs::ctr)
+    int screen_rounds = SCREEN_ROUNDS_DEFAULT;  // NICNES_SCREEN_ROUNDS: certify rounds of an over-cap lane (ScreenArgs::rounds)
     int exact_left = 0;
     int last_bounded = 0;
     int last_decode_bounded = 0;      // nicnes_last_decode_lse: the lse mode of the last decode enqueued
@@ -355,8 +356,8 @@ void ensure_screen(nicnes_handle* h) {
     bool ok = hipMalloc((void**)&h->screen_cap, (size_t)wgs * SCREEN_CAP_WORDS(h->V1) * sizeof(uint32_t)) == hipSuccess;
     if (ok) ok = hipMalloc((void**)&h->screen_norm, (size_t)h->cfg.max_members * 4 * sizeof(float)) == hipSuccess;
     if (ok && !h->screen_ctr)
-        ok = hipMalloc((void**)&h->screen_ctr, 2 * sizeof(unsigned long long)) == hipSuccess &&
-             hipMemset(h->screen_ctr, 0, 2 * sizeof(unsigned long long)) == hipSuccess;
+        ok = hipMalloc((void**)&h->screen_ctr, SCREEN_CTR_WORDS * sizeof(unsigned long long)) == hipSuccess &&
+             hipMemset(h->screen_ctr, 0, SCREEN_CTR_WORDS * sizeof(unsigned long long)) == hipSuccess;
     if (ok) {
         h->screen_wgs = wgs;
         return;
@@ -503,6 +504,8 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
         if (sc && sc[0] >= '0' && sc[0] <= '2' && sc[1] == 0) h->screen_mode = sc[0] - '0';
         const char* se = getenv("NICNES_SCREEN_EPS_SCALE");
         if (se && se[0]) h->screen_scale = std::max(1.0f, (float)atof(se));
+        const char* sr = getenv("NICNES_SCREEN_ROUNDS");
+        if (sr && sr[0]) h->screen_rounds = std::min(SCREEN_ROUNDS_MAX, std::max(1, atoi(sr)));
     }
     {
         int ncu = 0;
@@ -1139,7 +1142,7 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     }
     if ((int64_t)count * nslabs * S > h->part_cap)
         return fail(h, NICNES_ERR_INVALID, "decode split beyond the partial-state buffer (nicnes_set_decode_split)");
-    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr};
+    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr, h->screen_rounds};
     // automatic: from one workgroup per CU on (P = 256, B = 128: 15.7 ms an iteration screened against 23.05 ms
     // unscreened; with the certify spread over the workgroup a launch of one round of workgroups no longer
     // waits on a slow one). Fewer workgroups than CUs: not measured, the fp32 loop as before
@@ -1452,7 +1455,7 @@ static int split_decode_impl(nicnes_handle* h, nicnes_split* sp, int32_t first, 
     // counter read-back belong to the evaluates
     const bool bounded = h->bounded_mode == 1 || (h->bounded_mode == 2 && h->exact_left == 0);
     p.bounded_lse = bounded ? 1 : 0;
-    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr};
+    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr, h->screen_rounds};
     const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)n_pm * nslabs >= h->n_cu);
     if (screen_on && !p.lp && bounded && G == 4 && S == 1 && h->screen_cap && h->screen_norm &&
         (int64_t)n_pm * nslabs <= h->screen_wgs && n_pm <= h->cfg.max_members) {
@@ -1785,6 +1788,15 @@ int nicnes_screen_stats(nicnes_handle* h, int64_t* out2_host) {
     if (h->screen_ctr) HIPC(h, hipMemcpy(st, h->screen_ctr, sizeof st, hipMemcpyDeviceToHost));
     out2_host[0] = (int64_t)st[0];
     out2_host[1] = (int64_t)st[1];
+    return NICNES_OK;
+}
+
+int nicnes_screen_reasons(nicnes_handle* h, int64_t* out16_host) {
+    if (!h || !out16_host) return NICNES_ERR_INVALID;
+    unsigned long long st[SCREEN_CTR_WORDS] = {0};
+    HIPC(h, hipSetDevice(h->device));
+    if (h->screen_ctr) HIPC(h, hipMemcpy(st, h->screen_ctr, sizeof st, hipMemcpyDeviceToHost));
+    for (int i = 2; i < SCREEN_CTR_WORDS; ++i) out16_host[i - 2] = (int64_t)st[i];
     return NICNES_OK;
 }
 
@@ -2540,7 +2552,7 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
     p.bounded_lse = bounded ? 1 : 0;
     h->last_decode_bounded = (bounded && !p.lp) ? 1 : 0;
     const int rows = h->B, nslabs = nslabs_of(rows, 4);
-    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr};
+    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr, h->screen_rounds};
     const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)count * nslabs >= h->n_cu);
     if (!coop_S && screen_on && !p.lp && bounded && h->screen_cap && h->screen_norm &&
         (int64_t)count * nslabs <= h->screen_wgs) {         // screening is a property of the fused path

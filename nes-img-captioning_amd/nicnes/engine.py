@@ -690,8 +690,17 @@ class Engine:
         check(self.L.nicnes_stats(self.h, out), self.h, 'stats')
         sc = (ctypes.c_int64 * 2)()
         check(self.L.nicnes_screen_stats(self.h, sc), self.h, 'screen_stats')
-        return {'tie_fallbacks': out[0], 'sample_stage_fallbacks': out[1], 'coop_timeouts': out[2],
-                'sample_slot_timeouts': out[3], 'screen_candidates': sc[0], 'screen_fallback_rows': sc[1]}
+        sr = (ctypes.c_int64 * 16)()
+        check(self.L.nicnes_screen_reasons(self.h, sr), self.h, 'screen_reasons')
+        d = {'tie_fallbacks': out[0], 'sample_stage_fallbacks': out[1], 'coop_timeouts': out[2],
+             'sample_slot_timeouts': out[3], 'screen_candidates': sc[0], 'screen_fallback_rows': sc[1],
+             'screen_rows_over_cap': sr[0], 'screen_rows_undecided': sr[1], 'screen_rows_evicted': sr[2],
+             'screen_rows_nonfinite': sr[3], 'screen_rows_settled_later': sr[4], 'screen_resweep_rows': sr[5],
+             'screen_resweep_steps': sr[6], 'screen_resweep_waves': sr[15]}
+        # over-cap rows by the certify rounds their fuller lane needs at least (the last: 9 or more); plain integers,
+        # so that callers can subtract two stats() key by key
+        d.update({'screen_over_cap_rounds_%d' % (k + 2): sr[7 + k] for k in range(8)})
+        return d
 
 
 METRIC_KEYS = ('Bleu_1', 'Bleu_2', 'Bleu_3', 'Bleu_4', 'ROUGE_L', 'CIDEr')   # COCOEvalCap's keys (no java scorers)
