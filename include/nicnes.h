@@ -232,6 +232,44 @@ int nicnes_split_score(nicnes_handle* h, nicnes_split* split, int32_t first, int
 int nicnes_split_evaluate(nicnes_handle* h, nicnes_split* split, int32_t first, int32_t count, int64_t* totals_out_dev,
                           double* metrics_out_dev, double* row_cider_out_dev, int32_t* seq_out, void* stream);
 
+/* A resident training set: every image of the training split on the GPU, so that an iteration's batches are drawn by
+ * image index with device copies instead of being read, stacked and uploaded by the host (replaces what
+ * src/captioning/dataloader.py:148-203 get_batch assembles and nic_nes_worker.py:121-128 hands to every member's
+ * rollout: fc_feats and gts of the drawn images). Owned by the handle (destroyed with it), several may exist at once.
+ * nicnes_trainset_create copies its arrays before it returns (synchronising; each may be a host or a device pointer):
+ * fc [N, F] fp32; ref_tokens [n_refs, seq_length] and img_ref_start [N + 1] in the layout of nicnes_set_batch. It
+ * checks once what nicnes_set_batches checks per call (the ranges tile [0, n_refs), every image has >= 1 reference)
+ * and that every token lies in [0, vocab_size], and keeps a host copy of every image's reference count. N <= 2^24.
+ * fc may be NULL: the rows are then zeros until nicnes_trainset_write_fc writes them, so that a caller who reads the
+ * split in chunks never holds it whole, on the host or in a second device buffer. */
+typedef struct nicnes_trainset nicnes_trainset;
+int nicnes_trainset_create(nicnes_handle* h, const float* fc, int32_t N, const int32_t* ref_tokens, int32_t n_refs,
+                           const int32_t* img_ref_start, nicnes_trainset** out, void* stream);
+/* Rows [first, first + count) of the set's fc <- fc [count, F] fp32 (a host or a device pointer, copied before return;
+ * synchronises `stream` first): the chunked form of nicnes_trainset_create's fc argument (dataloader.py:209-243, one
+ * image's fc feature at a time). A range outside [0, N) is NICNES_ERR_INVALID. */
+int nicnes_trainset_write_fc(nicnes_handle* h, nicnes_trainset* ts, int32_t first, int32_t count, const float* fc,
+                             void* stream);
+int nicnes_trainset_destroy(nicnes_handle* h, nicnes_trainset* ts);
+/* nicnes_set_batches for images image_ix_host [n_batches * B] of the set (a HOST array of indices in [0, N), copied
+ * before return; batch g holds entries g * B .. g * B + B - 1; an image may occur any number of times): afterwards the
+ * handle is in the state nicnes_set_batches leaves for the same images in the same order (fc, B, n_batches, the
+ * reference ranges, the cooked reference vectors, the per-image n-gram tables), except that fc, the reference rows
+ * and the starts live in buffers the handle owns, gathered there on `stream` (dataloader.py:148-203 get_batch without
+ * the host: one gather of fc rows, one of label rows). n_refs, the starts and the largest reference count come from
+ * the host's copy of the counts: the call only enqueues, with no copy back and no wait, unless a buffer has to grow
+ * (B > max_batch, more references than max_refs, more images than the image capacity: as nicnes_set_batches,
+ * synchronising). The indices and starts travel through pinned staging of the handle, a slot of which is reused only
+ * after the copy that read it has run. NICNES_ERR_INVALID before anything is enqueued or changed (the batch held
+ * before still evaluates): an index outside [0, N), B or n_batches outside nicnes_set_batches' limits, a set that is
+ * not this handle's (or destroyed), no df table. nicnes_set_df_table invalidates a drawn batch as any other. */
+int nicnes_draw_batches(nicnes_handle* h, nicnes_trainset* ts, const int32_t* image_ix_host, int32_t n_batches, int32_t B,
+                        void* stream);
+/* Test entry (no reference counterpart): the batch arrays the handle currently reads, whichever call set them
+ * (nicnes_set_batches' borrowed buffers or a draw's own), copied to caller DEVICE buffers (each nullable): fc_out
+ * [n_batches * B, F] fp32, refs_out [n_refs, seq_length] int32, starts_out [n_batches * B + 1] int32. Only enqueues. */
+int nicnes_test_batch_state(nicnes_handle* h, float* fc_out, int32_t* refs_out, int32_t* starts_out, void* stream);
+
 /* Centred ranks + antithetic weights over the WHOLE population, replaces
  * NESMaster.compute_centered_ranks and the weights line of gradient_estimate
  * (src/algorithm/nic_nes/nic_nes_master.py:170-205). fitness [P, 2] fp64 -> cr [P, 2] (or NULL),

@@ -21,10 +21,15 @@
 #include "decode_kernel.h"
 #include "update_kernels.h"
 #include "sensitivity.h"
+#include "trainset_kernels.h"
+// the resident training set's two gather kernels and their launchers live in this translation unit (so the library
+// keeps its five code objects), ahead of this file's own kernels, whose machine code and order stay as they were
+#include "trainset_kernels.hip"
 
 #define SCREEN_DEFAULT 2   // the bf16-screened logit loop of the fused greedy-only decode: 0 off, 1 on,
                            // 2 automatic: on when the decode has more workgroups than the GPU has CUs
 #define MB_RING 4   // pinned staging slots of the member -> batch map (nicnes_evaluate_batches)
+#define DR_RING 4   // pinned staging slots of a draw's image indices and reference starts (nicnes_draw_batches)
 
 struct nicnes_handle {
     nicnes_config cfg;
@@ -59,7 +64,21 @@ struct nicnes_handle {
     int mb_next = 0;
     int32_t n_refs = 0;
     const int32_t* img_ref_start = nullptr;
+    const int32_t* ref_tokens = nullptr;   // the batch's reference rows [n_refs, T] (nicnes_test_batch_state)
     bool batch_set = false;
+    // nicnes_draw_batches: the batch buffers a draw gathers into (owned; h->fc, ref_tokens and img_ref_start point at
+    // them after a draw), the device copy of the staged words and the pinned ring they travel through. A slot holds
+    // [n_img] image indices then [n_img + 1] destination starts, and is reused only after its copy has run (its event)
+    float* dr_fc = nullptr;           // [dr_img_cap, F]
+    int32_t* dr_refs = nullptr;       // [dr_ref_cap, T]
+    int32_t* dr_start = nullptr;      // [dr_img_cap + 1]
+    int32_t* dr_stage = nullptr;      // [2 * dr_img_cap + 1]
+    int32_t dr_img_cap = 0, dr_ref_cap = 0;
+    int32_t* dr_pin[DR_RING] = {};
+    size_t dr_pin_cap[DR_RING] = {};  // in int32 words
+    hipEvent_t dr_ev[DR_RING] = {};
+    bool dr_used[DR_RING] = {};
+    int dr_next = 0;
 
     const uint64_t* df_keys = nullptr;
     const double* df_vals = nullptr;
@@ -177,6 +196,7 @@ struct nicnes_handle {
     int64_t t_prev = 0;
     int theta_fp32_prev = 0;
     std::vector<nicnes_split*> splits;        // resident evaluation splits (nicnes_split_create), freed with the handle
+    std::vector<struct nicnes_trainset*> trainsets;   // resident training sets (nicnes_trainset_create), likewise
     struct nicnes_es* es = nullptr;           // nic_es state (nicnes_es_create), freed with the handle
 };
 
@@ -238,6 +258,17 @@ struct nicnes_split {
     uint64_t* zero_idx = nullptr;
     int32_t* block = nullptr;
     float* part = nullptr;
+};
+
+// A resident training set (nicnes_trainset_create): every training image's fc row and raw reference rows on the
+// device, and the host's copy of what a draw needs without asking the device: each image's reference count.
+struct nicnes_trainset {
+    nicnes_handle* h = nullptr;
+    int32_t N = 0, n_refs = 0;
+    float* fc = nullptr;              // [N, F]
+    int32_t* ref_tokens = nullptr;    // [n_refs, T]
+    int32_t* img_ref_start = nullptr; // [N + 1]
+    std::vector<int32_t> count;       // [N] references per image (host)
 };
 
 namespace {
@@ -555,21 +586,24 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
 }
 
 static void split_free(nicnes_split* sp);
+static void trainset_free(nicnes_trainset* ts);
 
 int nicnes_destroy(nicnes_handle* h) {
     if (!h) return NICNES_OK;
     (void)hipSetDevice(h->device);
     if (h->comm && h->comm_owned) (void)ncclCommDestroy(h->comm);
-    if (!h->splits.empty()) (void)hipDeviceSynchronize();
+    if (!h->splits.empty() || !h->trainsets.empty()) (void)hipDeviceSynchronize();
     for (nicnes_split* sp : h->splits) split_free(sp);
     h->splits.clear();
+    for (nicnes_trainset* ts : h->trainsets) trainset_free(ts);
+    h->trainsets.clear();
     (void)nicnes_es_free(h);
     void* bufs[] = {h->theta64, h->theta32, h->m, h->v, h->ref_keys, h->ref_vec, h->ref_count, h->ref_len2,
                     h->ref_norm, h->nidx, h->seq, h->lp, h->row_scores, h->dscratch, h->stats, h->partials, h->norms,
                     h->hash_keys, h->hash_vals, h->img_hkey, h->img_hrow, h->img_vr, h->alive, h->part,
                     h->rank_key, h->rank_idx, h->mbatch, h->mut_vec, h->dbuf, h->didx, h->noise_sc, h->coop_ctr,
                     h->zero_noise, h->zero_idx, h->sens_tok, h->su, h->base_scores, h->slog, h->slog_slots, h->zcount,
-                    h->screen_cap, h->screen_norm, h->screen_ctr};
+                    h->screen_cap, h->screen_norm, h->screen_ctr, h->dr_fc, h->dr_refs, h->dr_start, h->dr_stage};
     if (h->sens) nicnes_sens_destroy(h->sens);
     for (void* p : bufs)
         if (p) (void)hipFree(p);
@@ -582,6 +616,13 @@ int nicnes_destroy(nicnes_handle* h) {
             (void)hipEventDestroy(h->mb_ev[i]);
         }
         if (h->mb_pin[i]) (void)hipHostFree(h->mb_pin[i]);
+    }
+    for (int i = 0; i < DR_RING; ++i) {
+        if (h->dr_ev[i]) {
+            (void)hipEventSynchronize(h->dr_ev[i]);
+            (void)hipEventDestroy(h->dr_ev[i]);
+        }
+        if (h->dr_pin[i]) (void)hipHostFree(h->dr_pin[i]);
     }
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
@@ -749,6 +790,7 @@ int nicnes_set_batches(nicnes_handle* h, const float* fc, int32_t n_batches, int
     h->n_img = n_img;
     h->n_refs = n_refs;
     h->img_ref_start = img_ref_start;
+    h->ref_tokens = ref_tokens;
     CiderTables tb = tables_of(h);
     HIPC(h, nicnes_launch_cook_refs(ref_tokens, n_refs, h->cfg.seq_length, &tb, (hipStream_t)stream));
     // per-image n-gram tables when every image has at most IMG_MAXR references (else the
@@ -765,6 +807,230 @@ int nicnes_set_batches(nicnes_handle* h, const float* fc, int32_t n_batches, int
 int nicnes_set_batch(nicnes_handle* h, const float* fc, int32_t B, const int32_t* ref_tokens, int32_t n_refs,
                      const int32_t* img_ref_start, void* stream) {
     return nicnes_set_batches(h, fc, 1, B, ref_tokens, n_refs, img_ref_start, stream);
+}
+
+// ---- resident training sets ---------------------------------------------------------------------------------------
+static void trainset_free(nicnes_trainset* ts) {
+    void* bufs[] = {ts->fc, ts->ref_tokens, ts->img_ref_start};
+    for (void* q : bufs)
+        if (q) (void)hipFree(q);
+    delete ts;
+}
+
+static bool trainset_of(const nicnes_handle* h, const nicnes_trainset* ts) {
+    return h && ts && std::find(h->trainsets.begin(), h->trainsets.end(), ts) != h->trainsets.end();
+}
+
+int nicnes_trainset_create(nicnes_handle* h, const float* fc, int32_t N, const int32_t* ref_tokens, int32_t n_refs,
+                           const int32_t* img_ref_start, nicnes_trainset** out, void* stream) {
+    if (!h || !ref_tokens || !img_ref_start || !out) return NICNES_ERR_INVALID;   // fc NULL: rows written later
+    *out = nullptr;
+    if (N < 1 || N > (1 << 24)) return fail(h, NICNES_ERR_INVALID, "N out of [1, 2^24]");
+    const size_t F = (size_t)h->cfg.fc_feat_size, T = (size_t)h->cfg.seq_length;
+    if (n_refs < N || (int64_t)n_refs * (int64_t)T > INT32_MAX) return fail(h, NICNES_ERR_INVALID, "n_refs out of range");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipStreamSynchronize(s));        // the caller's arrays may have been written on its stream
+    // what nicnes_set_batches checks per call, once: the ranges tile [0, n_refs) and every image has a reference
+    std::vector<int32_t> st((size_t)N + 1);
+    HIPC(h, hipMemcpy(st.data(), img_ref_start, st.size() * sizeof(int32_t), hipMemcpyDefault));
+    bool ok = st[0] == 0 && st[N] == n_refs;
+    for (int b = 0; b < N && ok; ++b) ok = st[b + 1] > st[b];
+    if (!ok)
+        return fail(h, NICNES_ERR_INVALID,
+                    "img_ref_start must start at 0, end at n_refs and give every image >= 1 reference");
+    // what Engine.set_batches checks on the host: a token outside the vocabulary would alias another word in the
+    // scorer's 14-bit key fields
+    std::vector<int32_t> tok((size_t)n_refs * T);
+    HIPC(h, hipMemcpy(tok.data(), ref_tokens, tok.size() * sizeof(int32_t), hipMemcpyDefault));
+    for (int32_t t : tok)
+        if (t < 0 || t > h->cfg.vocab_size) return fail(h, NICNES_ERR_INVALID, "reference token outside [0, vocab_size]");
+    nicnes_trainset* ts = new nicnes_trainset();
+    ts->h = h;
+    ts->N = N;
+    ts->n_refs = n_refs;
+    ts->count.resize((size_t)N);
+    for (int b = 0; b < N; ++b) ts->count[(size_t)b] = st[b + 1] - st[b];
+    auto run = [&]() -> int {
+        int rc = dalloc(h, &ts->fc, (size_t)N * F);
+        if (!rc) rc = dalloc(h, &ts->ref_tokens, tok.size());
+        if (!rc) rc = dalloc(h, &ts->img_ref_start, st.size());
+        if (rc) return rc;
+        if (fc)
+            HIPC(h, hipMemcpy(ts->fc, fc, (size_t)N * F * sizeof(float), hipMemcpyDefault));
+        else                                 // zeros until nicnes_trainset_write_fc fills the rows
+            HIPC(h, hipMemset(ts->fc, 0, (size_t)N * F * sizeof(float)));
+        HIPC(h, hipMemcpy(ts->ref_tokens, tok.data(), tok.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPC(h, hipMemcpy(ts->img_ref_start, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPC(h, hipDeviceSynchronize());
+        return NICNES_OK;
+    };
+    const int rc = run();
+    if (rc) {
+        trainset_free(ts);
+        return rc;
+    }
+    h->trainsets.push_back(ts);
+    *out = ts;
+    return NICNES_OK;
+}
+
+int nicnes_trainset_write_fc(nicnes_handle* h, nicnes_trainset* ts, int32_t first, int32_t count, const float* fc,
+                             void* stream) {
+    if (!h || !fc) return NICNES_ERR_INVALID;
+    if (!trainset_of(h, ts)) return fail(h, NICNES_ERR_INVALID, "not a training set of this handle");
+    if (first < 0 || count < 1 || (int64_t)first + count > ts->N)
+        return fail(h, NICNES_ERR_INVALID, "rows [first, first + count) outside the set");
+    const size_t F = (size_t)h->cfg.fc_feat_size;
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipStreamSynchronize((hipStream_t)stream));   // the caller's rows, and a gather still reading the set
+    HIPC(h, hipMemcpy(ts->fc + (size_t)first * F, fc, (size_t)count * F * sizeof(float), hipMemcpyDefault));
+    return NICNES_OK;
+}
+
+int nicnes_trainset_destroy(nicnes_handle* h, nicnes_trainset* ts) {
+    if (!h) return NICNES_ERR_INVALID;
+    if (!ts) return NICNES_OK;
+    if (!trainset_of(h, ts)) return fail(h, NICNES_ERR_INVALID, "not a training set of this handle");
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipDeviceSynchronize());         // a gather of a draw may still read the set
+    h->trainsets.erase(std::find(h->trainsets.begin(), h->trainsets.end(), ts));
+    trainset_free(ts);
+    return NICNES_OK;
+}
+
+// the draw's own batch buffers for n_img images and n_refs reference rows (grown outside every launch)
+static int draw_grow(nicnes_handle* h, int n_img, int n_refs) {
+    const size_t F = (size_t)h->cfg.fc_feat_size, T = (size_t)h->cfg.seq_length;
+    if (n_img > h->dr_img_cap) {
+        HIPC(h, hipDeviceSynchronize());
+        void* old[] = {h->dr_fc, h->dr_start, h->dr_stage};
+        for (void* q : old)
+            if (q) (void)hipFree(q);
+        h->dr_fc = nullptr; h->dr_start = nullptr; h->dr_stage = nullptr;
+        h->dr_img_cap = 0;
+        const size_t cap = (size_t)std::max(n_img, h->img_cap);
+        int rc = dalloc(h, &h->dr_fc, cap * F);
+        if (!rc) rc = dalloc(h, &h->dr_start, cap + 1);
+        if (!rc) rc = dalloc(h, &h->dr_stage, 2 * cap + 1);
+        if (rc) return rc;
+        h->dr_img_cap = (int32_t)cap;
+    }
+    if (n_refs > h->dr_ref_cap) {
+        HIPC(h, hipDeviceSynchronize());
+        if (h->dr_refs) (void)hipFree(h->dr_refs);
+        h->dr_refs = nullptr;
+        h->dr_ref_cap = 0;
+        const size_t cap = (size_t)std::max(n_refs, h->cfg.max_refs);
+        int rc = dalloc(h, &h->dr_refs, cap * T);
+        if (rc) return rc;
+        h->dr_ref_cap = (int32_t)cap;
+    }
+    return NICNES_OK;
+}
+
+int nicnes_draw_batches(nicnes_handle* h, nicnes_trainset* ts, const int32_t* image_ix_host, int32_t n_batches, int32_t B,
+                        void* stream) {
+    if (!h || !image_ix_host) return NICNES_ERR_INVALID;
+    if (!trainset_of(h, ts)) return fail(h, NICNES_ERR_INVALID, "not a training set of this handle");
+    if (B < 1 || B > 1024) return fail(h, NICNES_ERR_INVALID, "B out of [1, 1024]");
+    if (n_batches < 1 || (int64_t)n_batches * B > (1 << 20)) return fail(h, NICNES_ERR_INVALID, "n_batches out of range");
+    if (!h->df_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_df_table first");
+    const int n_img = n_batches * B;
+    // the host's own copy of the counts gives n_refs and the largest reference count: nothing is read back
+    int64_t total = 0;
+    int maxr = 0;
+    for (int i = 0; i < n_img; ++i) {
+        const int32_t ix = image_ix_host[i];
+        if (ix < 0 || ix >= ts->N) return fail(h, NICNES_ERR_INVALID, "image index outside [0, N)");
+        total += ts->count[(size_t)ix];
+        maxr = std::max(maxr, ts->count[(size_t)ix]);
+    }
+    if (total * h->cfg.seq_length > INT32_MAX) return fail(h, NICNES_ERR_INVALID, "too many reference rows in one draw");
+    const int n_refs = (int)total;
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    // growth as in nicnes_set_batches (synchronising then), and the draw's own buffers with it
+    {
+        int rc = NICNES_OK;
+        if (B > h->cfg.max_batch || n_refs > h->cfg.max_refs || n_img > h->img_cap) {
+            HIPC(h, hipDeviceSynchronize());
+            h->batch_set = false;            // the batch held loses its cooked buffers: whatever fails below, it is gone
+            if (n_refs > h->cfg.max_refs) rc = alloc_refs(h, std::max(n_refs, 2 * h->cfg.max_refs));
+            if (!rc && B > h->cfg.max_batch) rc = alloc_batch(h, B);
+            if (!rc && n_img > h->img_cap) rc = alloc_images(h, n_img);
+        }
+        const bool own = h->fc == h->dr_fc && h->fc;    // the batch held lives in the buffers about to move
+        if (!rc && (n_img > h->dr_img_cap || n_refs > h->dr_ref_cap)) {
+            if (own) h->batch_set = false;
+            rc = draw_grow(h, n_img, n_refs);
+        }
+        if (rc) {
+            h->batch_set = false;
+            return rc;
+        }
+    }
+    // staging: [n_img] indices, [n_img + 1] destination starts, through a pinned slot whose last copy has run
+    const size_t words = 2 * (size_t)n_img + 1;
+    const int slot = h->dr_next;
+    h->dr_next = (slot + 1) % DR_RING;
+    if (!h->dr_ev[slot]) HIPC(h, hipEventCreateWithFlags(&h->dr_ev[slot], hipEventDisableTiming));
+    if (h->dr_used[slot]) HIPC(h, hipEventSynchronize(h->dr_ev[slot]));
+    h->dr_used[slot] = false;
+    if (words > h->dr_pin_cap[slot]) {
+        if (h->dr_pin[slot]) (void)hipHostFree(h->dr_pin[slot]);
+        h->dr_pin[slot] = nullptr;
+        h->dr_pin_cap[slot] = 0;
+        const size_t cap = std::max(words, 2 * (size_t)h->img_cap + 1);
+        if (hipHostMalloc((void**)&h->dr_pin[slot], cap * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
+            return fail(h, NICNES_ERR_HIP, "hipHostMalloc");
+        h->dr_pin_cap[slot] = cap;
+    }
+    int32_t* pin = h->dr_pin[slot];
+    std::memcpy(pin, image_ix_host, (size_t)n_img * sizeof(int32_t));
+    int32_t* dst = pin + n_img;
+    dst[0] = 0;
+    for (int i = 0; i < n_img; ++i) dst[i + 1] = dst[i] + ts->count[(size_t)image_ix_host[i]];
+    h->batch_set = false;                    // until everything below is enqueued
+    HIPC(h, hipMemcpyAsync(h->dr_stage, pin, words * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPC(h, hipEventRecord(h->dr_ev[slot], s));
+    h->dr_used[slot] = true;
+    HIPC(h, nicnes_launch_gather_fc(ts->fc, h->dr_stage, n_img, h->cfg.fc_feat_size, h->dr_fc, s));
+    HIPC(h, nicnes_launch_gather_refs(ts->ref_tokens, ts->img_ref_start, h->dr_stage, h->dr_stage + n_img, n_img,
+                                      h->cfg.seq_length, h->dr_refs, h->dr_start, s));
+    // from here on: nicnes_set_batches on the handle's own buffers
+    h->fc = h->dr_fc;
+    h->B = B;
+    h->n_batches = n_batches;
+    h->n_img = n_img;
+    h->n_refs = n_refs;
+    h->img_ref_start = h->dr_start;
+    h->ref_tokens = h->dr_refs;
+    CiderTables tb = tables_of(h);
+    HIPC(h, nicnes_launch_cook_refs(h->dr_refs, n_refs, h->cfg.seq_length, &tb, s));
+    h->img_tables = maxr <= IMG_MAXR;
+    if (h->img_tables) {
+        HIPC(h, hipMemsetAsync(h->img_vr, 0, (size_t)n_img * IMG_ROWS * IMG_MAXR * sizeof(double), s));
+        HIPC(h, nicnes_launch_img_ngrams(h->dr_start, n_img, &tb, s));
+    }
+    h->batch_set = true;
+    return NICNES_OK;
+}
+
+int nicnes_test_batch_state(nicnes_handle* h, float* fc_out, int32_t* refs_out, int32_t* starts_out, void* stream) {
+    if (!h) return NICNES_ERR_INVALID;
+    if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    const size_t F = (size_t)h->cfg.fc_feat_size, T = (size_t)h->cfg.seq_length;
+    if (fc_out)
+        HIPC(h, hipMemcpyAsync(fc_out, h->fc, (size_t)h->n_img * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (refs_out)
+        HIPC(h, hipMemcpyAsync(refs_out, h->ref_tokens, (size_t)h->n_refs * T * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (starts_out)
+        HIPC(h, hipMemcpyAsync(starts_out, h->img_ref_start, ((size_t)h->n_img + 1) * sizeof(int32_t),
+                               hipMemcpyDeviceToDevice, s));
+    return NICNES_OK;
 }
 
 int nicnes_noise_indices(nicnes_handle* h, uint64_t iteration, int32_t member_begin, int32_t count, uint64_t* out,

@@ -30,7 +30,8 @@ EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_create', 'nicne
            'nicnes_es_create', 'nicnes_es_free', 'nicnes_es_set_mutation', 'nicnes_es_set_parent',
            'nicnes_es_set_parent_count', 'nicnes_es_get_row', 'nicnes_es_row_stats', 'nicnes_es_evaluate',
            'nicnes_es_offspring', 'nicnes_es_select', 'nicnes_es_advance', 'nicnes_es_set_elite',
-           'nicnes_es_load_theta', 'nicnes_set_decode_es', 'nicnes_decode_path_es', 'nicnes_allgather_fitness_es']
+           'nicnes_es_load_theta', 'nicnes_set_decode_es', 'nicnes_decode_path_es', 'nicnes_allgather_fitness_es',
+           'nicnes_trainset_create', 'nicnes_trainset_write_fc', 'nicnes_trainset_destroy', 'nicnes_draw_batches', 'nicnes_test_batch_state']
 
 
 class NicnesConfig(ctypes.Structure):
@@ -118,6 +119,11 @@ def lib(path=None):
         'nicnes_split_decode': (c.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         'nicnes_split_score': (c.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
         'nicnes_split_evaluate': (c.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+        'nicnes_trainset_create': (c.c_int, [vp, vp, i32, vp, i32, vp, c.POINTER(vp), vp]),
+        'nicnes_trainset_write_fc': (c.c_int, [vp, vp, i32, i32, vp, vp]),
+        'nicnes_trainset_destroy': (c.c_int, [vp, vp]),
+        'nicnes_draw_batches': (c.c_int, [vp, vp, vp, i32, i32, vp]),
+        'nicnes_test_batch_state': (c.c_int, [vp, vp, vp, vp, vp]),
         'nicnes_es_create': (c.c_int, [vp, i32, i32]),
         'nicnes_es_free': (c.c_int, [vp]),
         'nicnes_es_set_mutation': (c.c_int, [vp, i32]),

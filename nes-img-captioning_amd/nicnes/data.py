@@ -22,6 +22,9 @@ Differences, on purpose:
     is executed. A JSON / npz export (`save_df_table`) is offered as the portable form.
   * the random generator is a seeded `random.Random` owned by the loader instead of the module-wide
     `random` state, so a master and its tests can replay a batch sequence.
+
+ResidentTrainLoader wraps a CocoFcDataLoader for the training split held on the GPU (engine.TrainSet): the same walk of
+the split, but a batch is a DrawnBatch of image indices that Engine.draw_batches gathers on the device.
 """
 import collections
 import io
@@ -158,6 +161,103 @@ class CocoFcDataLoader:
                 'bounds': {'it_pos_now': self.iterators[split], 'it_max': len(self.split_ix[split]),
                            'wrapped': wrapped},
                 'infos': infos}
+
+
+# ---------------------------------------------------------------- resident training set -----------
+class DrawnBatch(dict):
+    """A training batch named by its images instead of carrying them: 'image_ix' (int32 [B], indices into
+    'trainset', an engine.TrainSet), 'bounds' and 'infos' as get_batch gives them, 'seq_per_img', and no fc rows.
+    A dict, so whoever reads a batch's 'bounds' or 'infos' reads them as from the host loader's; the masters hand it
+    to Engine.draw_batches (nes.draw_engine_batches)."""
+
+    def fc_rows(self):
+        """The batch's unique fc rows [B, F] fp32 on the host, read from the set's source on demand."""
+        return self['trainset'].fc_rows(self['image_ix'])
+
+
+class ResidentTrainLoader:
+    """CocoFcDataLoader's training batches, drawn from a training set held on the GPU.
+
+    At construction every image of `split` is read once (loader.fc_feature, the label store) and uploaded in chunks
+    as an engine.TrainSet; with fc_cache=PATH the rows are also written to one packed [N, F] .npy, which later starts
+    memory-map instead of opening N files (the file belongs to this info json, split and train_only). get_batch(split)
+    then walks the wrapped loader's own iterator: the same _next_ix calls, and the same get_captions calls for the
+    draws they take from the loader's random.Random (the label rows themselves are not used: the greedy and sampled
+    fitness read gts), so for one seed the image sequence, bounds, wrapped flags and epoch boundaries are the host
+    loader's. It returns a DrawnBatch. Other splits delegate to the wrapped loader unchanged."""
+
+    CHUNK_ROWS = 4096
+
+    def __init__(self, loader, engine, split='train', fc_cache=None):
+        self.loader, self.engine, self.split = loader, engine, split
+        self.images = sorted(loader.split_ix[split])            # set row r holds image self.images[r]
+        if not self.images:
+            raise ValueError('split %r has no images' % split)
+        self.row_of = {ix: r for r, ix in enumerate(self.images)}
+        N = len(self.images)
+        lab = loader.labels
+        gts = [lab.labels[lab.label_start_ix[ix] - 1: lab.label_end_ix[ix]] for ix in self.images]
+        first = np.asarray(loader.fc_feature(self.images[0]), np.float32)
+        F = int(first.shape[0])
+        fc = None
+        if fc_cache and os.path.exists(fc_cache):
+            fc = np.load(fc_cache, mmap_mode='r', allow_pickle=False)
+            if fc.shape != (N, F) or fc.dtype != np.float32:
+                raise ValueError('%s holds %s %s, the split needs (%d, %d) float32' % (fc_cache, fc.shape, fc.dtype, N, F))
+        elif fc_cache:
+            tmp = '%s.tmp.%d' % (fc_cache, os.getpid())     # per process: ranks starting together each write their own
+            out = np.lib.format.open_memmap(tmp, mode='w+', dtype=np.float32, shape=(N, F))
+            for c0 in range(0, N, self.CHUNK_ROWS):
+                for r in range(c0, min(c0 + self.CHUNK_ROWS, N)):
+                    out[r] = loader.fc_feature(self.images[r])
+            out.flush()
+            del out
+            os.replace(tmp, fc_cache)                       # atomic: a rank that mapped an earlier file keeps it
+            fc = np.load(fc_cache, mmap_mode='r', allow_pickle=False)
+        if fc is not None:
+            self.trainset = engine.make_trainset(fc, gts)
+        else:
+            self.trainset = engine.make_trainset(_FileRows(loader, self.images, F), gts,
+                                                 fc_rows=lambda ix: np.stack([loader.fc_feature(self.images[int(r)])
+                                                                              for r in ix]))
+
+    # what the masters and the validator read of a loader
+    def __getattr__(self, name):
+        if name == 'loader':
+            raise AttributeError(name)
+        return getattr(self.loader, name)
+
+    def get_batch(self, split, batch_size=None, seq_per_img=None):
+        if split != self.split:
+            return self.loader.get_batch(split, batch_size=batch_size, seq_per_img=seq_per_img)
+        ld = self.loader
+        batch_size = batch_size or ld.batch_size
+        seq_per_img = seq_per_img or ld.seq_per_img
+        rows, infos, wrapped = np.empty(batch_size, np.int32), [], False
+        for i in range(batch_size):
+            ix, w = ld._next_ix(split)
+            wrapped = wrapped or w
+            ld.get_captions(ix, seq_per_img)                    # for its draws: the host loader's rng sequence
+            rows[i] = self.row_of[ix]
+            img = ld.info['images'][ix]
+            infos.append({'ix': ix, 'id': img['id'], 'file_path': img.get('file_path')})
+        return DrawnBatch(image_ix=rows, trainset=self.trainset, seq_per_img=int(seq_per_img), infos=infos,
+                          bounds={'it_pos_now': ld.iterators[split], 'it_max': len(ld.split_ix[split]),
+                                  'wrapped': wrapped})
+
+    def close(self):
+        self.trainset.close()
+
+
+class _FileRows:
+    """The split's fc rows as an array-like over the per-image files: [N, F], sliced a chunk at a time by
+    engine.TrainSet's upload, so the whole split is never one host array."""
+
+    def __init__(self, loader, images, F):
+        self.loader, self.images, self.shape = loader, images, (len(images), F)
+
+    def __getitem__(self, sl):
+        return np.stack([np.asarray(self.loader.fc_feature(ix), np.float32) for ix in self.images[sl]])
 
 
 # ---------------------------------------------------------------- df table ------------------------

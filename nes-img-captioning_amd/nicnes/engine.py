@@ -170,6 +170,47 @@ class Engine:
         self.B = B
         self.n_batches = len(fcs)
 
+    def make_trainset(self, fc, gts, fc_rows=None):
+        """A resident training set (nicnes_trainset_create): fc [N, F] fp32 (a numpy array or memory map, uploaded
+        in chunks; or a tensor), gts per image an int array [n_i, seq_length] of zero-padded label rows. fc_rows:
+        optional callable (indices) -> host fc rows, for callers that want rows back (mutations.batch_fc); a numpy fc
+        serves as its own. Batches are then drawn from it by image index (draw_batches)."""
+        return TrainSet(self, fc, gts, fc_rows)
+
+    def draw_batches(self, trainset, image_ix):
+        """set_batches for images image_ix ([n_batches, B] or [B] indices into the set) of a resident training set,
+        gathered on the device (nicnes_draw_batches): only enqueues; the host sends the indices and nothing else."""
+        ix = np.ascontiguousarray(np.asarray(image_ix, np.int32))
+        if ix.ndim == 1:
+            ix = ix[None]
+        if ix.ndim != 2 or ix.shape[1] < 1:
+            raise ValueError('image_ix must be [n_batches, B] or [B]')
+        if trainset.engine is not self:
+            raise ValueError('the training set belongs to another engine')
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_draw_batches(self.h, trainset.ts, ix.ctypes.data_as(ctypes.c_void_p), int(ix.shape[0]),
+                                             int(ix.shape[1]), self._stream()), self.h, 'draw_batches')
+        self.B = int(ix.shape[1])
+        self.n_batches = int(ix.shape[0])
+
+    def test_batch_state(self, n_refs=None):
+        """Test entry: (fc [n_batches * B, F], reference rows [n_refs, seq_length], starts [n_batches * B + 1]) the
+        handle currently reads, whichever call set them; tensors on the GPU. The reference-row buffer is sized from
+        the handle's own starts (read back first: synchronises); n_refs, when given, must be that count."""
+        n_img = self.B * getattr(self, 'n_batches', 1)
+        starts = torch.empty(n_img + 1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_test_batch_state(self.h, None, None, _ptr(starts), self._stream()), self.h,
+                  'test_batch_state')
+            held = int(starts[-1].item())
+            if n_refs is not None and int(n_refs) != held:
+                raise ValueError('the handle holds %d reference rows, not %d' % (held, int(n_refs)))
+            fc = torch.empty((n_img, self.cfg.fc_feat_size), dtype=torch.float32, device=self.device)
+            refs = torch.empty((held, self.cfg.seq_length), dtype=torch.int32, device=self.device)
+            check(self.L.nicnes_test_batch_state(self.h, _ptr(fc), _ptr(refs), None, self._stream()), self.h,
+                  'test_batch_state')
+        return fc, refs, starts
+
     def make_split(self, fc, gts=None, df=None, ref_len_raw=None):
         """A resident evaluation split (nicnes_split_create): fc [N, F] fp32, gts per image an int array
         [n_i, seq_length] of zero-padded label rows (None: a decode-only split). df: the split's own document
@@ -827,3 +868,59 @@ class Split:
                                             _ptr(seq), e._stream()), e.h, 'split_evaluate')
         res = self._result(totals, metrics, rows, detail)
         return (res, seq) if return_seq else res
+
+
+class TrainSet:
+    """The training split's fc rows and label rows held on the GPU (nicnes_trainset_*; Engine.make_trainset):
+    Engine.draw_batches gathers an iteration's batches from it by image index."""
+
+    CHUNK_ROWS = 4096      # rows of one upload (32 MB at F = 2048)
+
+    def __init__(self, engine, fc, gts, fc_rows=None):
+        e = self.engine = engine
+        T, F = e.cfg.seq_length, e.cfg.fc_feat_size
+        if tuple(fc.shape[1:]) != (F,) or fc.shape[0] < 1:
+            raise ValueError('fc must be [N >= 1, fc_feat_size]')
+        self.N = int(fc.shape[0])
+        if len(gts) != self.N:
+            raise ValueError('gts has %d images, fc has %d rows' % (len(gts), self.N))
+        rows = [np.asarray(g, np.int32).reshape(-1, T) for g in gts]
+        self.counts = np.array([r.shape[0] for r in rows], np.int32)
+        start = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int32)
+        refs_np = np.ascontiguousarray(np.concatenate(rows, 0))
+        self._rows = fc_rows
+        fc_t = None
+        if isinstance(fc, torch.Tensor):       # the caller's tensor is copied: it holds the rows a second time
+            fc_t = fc.to(device=e.device, dtype=torch.float32).contiguous()
+        elif fc_rows is None:
+            self._rows = lambda ix, a=fc: np.asarray(a[np.asarray(ix, np.int64)], np.float32)
+        ts = ctypes.c_void_p()
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)     # noqa: E731  (host arrays: the call copies them)
+        with torch.cuda.device(e.device):
+            torch.cuda.current_stream().synchronize()
+            check(e.L.nicnes_trainset_create(e.h, _ptr(fc_t), self.N, vp(refs_np), int(refs_np.shape[0]), vp(start),
+                                             ctypes.byref(ts), e._stream()), e.h, 'trainset_create')
+            self.ts = ts
+            # host rows go straight into the set's own buffer, a chunk at a time: the split is never whole on the
+            # host, and never twice on the device
+            for c0 in range(0, self.N if fc_t is None else 0, self.CHUNK_ROWS):
+                part = np.ascontiguousarray(fc[c0:c0 + self.CHUNK_ROWS], np.float32)
+                check(e.L.nicnes_trainset_write_fc(e.h, ts, c0, int(part.shape[0]), vp(part), e._stream()), e.h,
+                      'trainset_write_fc')
+
+    def fc_rows(self, image_ix):
+        """Host fc rows [len(image_ix), F] fp32 of images of the set, read on demand from the source given at creation."""
+        if self._rows is None:
+            raise ValueError('this training set was made without a host source of its fc rows')
+        return np.ascontiguousarray(self._rows(np.asarray(image_ix, np.int64)), np.float32)
+
+    def close(self):
+        if getattr(self, 'ts', None) and getattr(self.engine, 'h', None):
+            self.engine.L.nicnes_trainset_destroy(self.engine.h, self.ts)
+        self.ts = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

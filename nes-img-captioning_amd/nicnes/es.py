@@ -370,15 +370,18 @@ class EngineESMaster:
         record."""
         import torch
         from ._lib import DecodeFault
-        from .nes import engine_batch
+        from .nes import engine_batch, is_drawn, draw_engine_batches
         e, spec, sc = self.e, self.spec, self.sched
         t0 = time.time()
         before = dict(sc.__dict__)
         sc.incr_iteration()
         g = sc.iteration
         sigma = sc.noise_stdev
-        fc, gts = engine_batch(batch, e) if isinstance(batch, dict) else batch
-        e.set_batch(fc, gts)
+        if is_drawn(batch):                # a batch of a resident training set: drawn on the device
+            draw_engine_batches(batch, e)
+        else:
+            fc, gts = engine_batch(batch, e) if isinstance(batch, dict) else batch
+            e.set_batch(fc, gts)
         parent_of = self.parents_of(g)
         begin, count = self.shard
         fit = self._gather_fitness(e.es_evaluate(g, begin, count, sigma, parent_of[begin:begin + count]))   # 1
@@ -506,6 +509,10 @@ def parse_args(argv=None):
     ap.add_argument('--log_dir', default=None)
     ap.add_argument('--data_root', default='.', help="directory the caption_options paths are relative to")
     ap.add_argument('--df_path', default=None, help='document-frequency table of the training split (data.load_df_table)')
+    ap.add_argument('--resident-train', action='store_true',
+                    help='hold the training split on the GPU and draw every batch there (data.ResidentTrainLoader)')
+    ap.add_argument('--fc-cache', default=None, metavar='PATH',
+                    help='with --resident-train: one packed [N, F] .npy of the split, written once, memory-mapped after')
     ap.add_argument('--noise_len', type=int, default=1 << 27)
     ap.add_argument('--decode', default=None, help="fused | auto | coop2 | coop4 (default: fused alone, auto over ranks)")
     return ap.parse_args(argv)
@@ -577,9 +584,11 @@ def main(argv=None):
         keys, vals = nicnes.df_table_arrays(df)
         eng.set_df_table(keys, vals, np.log(float(n)))
 
+        train = data.ResidentTrainLoader(loader, eng, fc_cache=args.fc_cache) if args.resident_train else loader
+
         def batches(bs):
             while True:
-                yield loader.get_batch('train', batch_size=bs)
+                yield train.get_batch('train', batch_size=bs)
         if num_val is None or num_val:
             validator = Validator(eng, loader, 'val', 5000 if num_val is None else int(num_val)) if rank == 0 else True
     decode = {None: None, 'fused': 'fused', 'auto': 'auto', 'coop2': ('coop', 2), 'coop4': ('coop', 4)}[args.decode]

@@ -24,7 +24,8 @@ import time
 import numpy as np
 import torch
 
-from .nes import NESTask, make_optimizer, state_dict_from_vector, param_shapes, EnginePolicy, engine_batch
+from .nes import (NESTask, make_optimizer, state_dict_from_vector, param_shapes, EnginePolicy, engine_batch, is_drawn,
+                  draw_engine_batches)
 from .population import PopulationRunner
 
 
@@ -137,9 +138,12 @@ class EngineMaster:
     def _set_batch(self, batch):
         """One batch (dict, or (fc, gts)) shared by every member, or a list of G batches (single_batch:
         false: member i uses batch i mod G). The batch object itself is kept: an id() of a freed batch
-        can be reused by the next one."""
+        can be reused by the next one. A data.DrawnBatch (or a list of them) is drawn on the device from its
+        resident training set instead of being uploaded."""
         if batch is not self._batch_key:
-            if isinstance(batch, list):
+            if is_drawn(batch):                 # batches of a resident training set: one draw for the whole list
+                self._n_batches = draw_engine_batches(batch, self.e)
+            elif isinstance(batch, list):
                 ub = [engine_batch(b, self.e) if isinstance(b, dict) else b for b in batch]
                 if len(ub) == 1:
                     self.e.set_batch(*ub[0])
@@ -337,6 +341,9 @@ class EngineMaster:
         for batch in self._batch_stream(batches):
             if done >= max_iterations:
                 break
+            if is_drawn(batch):
+                raise ValueError('run_dispatched ships every batch to the workers: give it the host loader, not a '
+                                 'ResidentTrainLoader (a DrawnBatch names rows of this process\'s GPU)')
             t0 = time.time()
             self.sched.incr_iteration()
             self._set_batch(batch)

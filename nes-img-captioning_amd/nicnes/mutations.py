@@ -133,10 +133,14 @@ class Mutator:
 
 
 def batch_fc(batch):
-    """Unique fc rows of a task batch: a reference batch dict, (fc, gts), or a list of either (the first)."""
+    """Unique fc rows of a task batch: a reference batch dict, (fc, gts), a data.DrawnBatch (its rows are read
+    from the resident set's source on demand), or a list of any of them (the first)."""
     from .nes import unique_batch
+    from .data import DrawnBatch
     if isinstance(batch, list):
         batch = batch[0]
+    if isinstance(batch, DrawnBatch):
+        return batch.fc_rows()
     if isinstance(batch, dict):
         return unique_batch(batch)[0]
     return np.asarray(batch[0], np.float32)

@@ -90,6 +90,28 @@ def engine_batch(data, engine, seq_per_img=5):
     return fc, gts
 
 
+def is_drawn(batch):
+    """A data.DrawnBatch, or a non-empty list of them: batches named by image index into a resident training set."""
+    from .data import DrawnBatch
+    if isinstance(batch, list):
+        return bool(batch) and all(isinstance(b, DrawnBatch) for b in batch)
+    return isinstance(batch, DrawnBatch)
+
+
+def draw_engine_batches(drawn, engine):
+    """engine_batch + set_batch(es) for DrawnBatches (one, or a list of G of one size and one set): ONE
+    Engine.draw_batches call of shape [G, B]. The sampled modes are told rows_per_image from the batch's
+    seq_per_img, as engine_batch tells them from the copies of a host batch. Returns G."""
+    drawn = drawn if isinstance(drawn, list) else [drawn]
+    ts = drawn[0]['trainset']
+    if any(d['trainset'] is not ts for d in drawn):
+        raise ValueError('the batches of one iteration must come from one training set')
+    if getattr(engine, 'fitness_mode', 0) in SAMPLED_FITNESS_CODES and hasattr(engine, 'set_rows_per_image'):
+        engine.set_rows_per_image(max(1, int(drawn[0]['seq_per_img'])))
+    engine.draw_batches(ts, np.stack([np.asarray(d['image_ix'], np.int32) for d in drawn]))
+    return len(drawn)
+
+
 def member_batches(batch_data, member_begin, count):
     """Per-member batch indices when batch_data is a list of G batches (member i uses batch i mod G),
     None for one shared batch."""
