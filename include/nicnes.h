@@ -344,7 +344,11 @@ int nicnes_allreduce_grad(nicnes_handle* h, float* gsum, void* stream);
  * the Adam kernel's own skip flag, so the NaN ratio of an applied step (0/0) is returned as a ratio, not an
  * error. The handle stays faulted until nicnes_clear_faults, or destroy it (the reference's worker process
  * dies and is restarted, main.py:107-141). */
-int nicnes_stats(nicnes_handle* h, int64_t* out4_host);
+/* out8_host [4..7], the screened decode's step queue (nicnes_set_decode_queue): [4] = tasks (member slab, step) run
+ * and [5] = waits that ran past their bound, both over the handle's life; [6] = member slabs the last queue launch
+ * counted finished, [7] = tasks it left in the ring (0 after a sound launch). A queue timeout also counts in [2]: it
+ * is a hand-off timeout and is contained and reported as one. */
+int nicnes_stats(nicnes_handle* h, int64_t* out8_host);
 
 /* Clear a contained decode fault (synchronising on the device): out2_host (nullable) receives the fault
  * counters [2], [3] of nicnes_stats before they are zeroed; the logit-slot claim flags are reset. theta, m
@@ -418,6 +422,20 @@ int nicnes_last_decode_lse(nicnes_handle* h, int32_t* bounded_host);
  * step goes to the fp32 loop. R bounds the weight, not the number of rounds: packing weights of 4 into rounds of 8 can
  * take a lane one round more than R. 1: no round after the first. */
 int nicnes_set_decode_screen(nicnes_handle* h, int32_t mode);
+/* Step queue of the screened decode (not a reference interface: the reference decodes a member's caption in one
+ * FCModel._sample call, src/captioning/nets.py:183-245, and has no dispatch of its own; DESIGN.md 5, "Step queue"): mode 1
+ * runs the screened fused decode (nicnes_set_decode_screen) as `workers` persistent workgroups that take (member slab,
+ * step) tasks from a FIFO ring on the device, so the launch ends within about a step of total work / workers instead of
+ * with the CU whose member slabs sum longest; mode 0 one workgroup per member slab; mode 2 (the default) the queue when
+ * the decode has more member slabs than workers. workers 0: the device's CU count. Tokens do not depend on it. env
+ * NICNES_DECODE_QUEUE=0/1/2 and NICNES_DECODE_QUEUE_WORKERS=n set the initial values. A wait in the queue that lasts
+ * 0.5 s is a decode fault (nicnes_stats). */
+int nicnes_set_decode_queue(nicnes_handle* h, int32_t mode, int32_t workers);
+/* The rule behind it, without a handle (pure; for tests and tools): for a screened fused decode of members x slabs
+ * member slabs on a device of n_cu CUs, out3_host = {1 when the queue kernel runs, its workgroups, the ring's slots (a
+ * power of two >= members x slabs)}. mode < 0: mode and workers from the environment variables above (defaults 2, 0). */
+int nicnes_decode_queue_plan(int32_t mode, int32_t workers, int32_t n_cu, int32_t members, int32_t slabs,
+                             int32_t* out3_host);
 /* the screened decodes' counters since create: [0] candidate ids captured, [1] rows the first certify round left
  * bad (before the certify rounds each sent its workgroup's step to the fp32 loop; nicnes_screen_reasons says what
  * became of them) */

@@ -18,7 +18,7 @@ struct DecodeParams {
     const double* sample_u;      // nullable: sampled decode (nets.py:210-231, fused path only): the uniform of
                                  // every (member, sign, row, logit step) [members, 2, B, T]; NULL = greedy
     float* scratch;              // nicnes_decode_scratch_floats(): lane-private c | h' | x0 | unfinished | h' (odd)
-    int32_t* stats;              // [0] exact-pass fallbacks (atomic), [1] sampled re-walks, [2] coop timeouts,
+    int32_t* stats;              // [0] exact-pass fallbacks (atomic), [1] sampled re-walks, [2] coop (and step queue) timeouts,
                                  // [3] sampled workgroups that found no free logit slot
     float* slog;                 // sampled steps kernel: slog_ns logit slots of nst * 16384 floats (> one per resident
                                  // workgroup): the logit loop stores each step's logits there, the pick reads them
@@ -74,6 +74,37 @@ struct ScreenArgs {
 #define SCREEN_ROUNDS_DEFAULT 2
 #define SCREEN_ROUNDS_MAX 64
 
+// The step queue of the screened fused decode (nicnes_decode_steps_screen_queue_kernel's third argument; ring == NULL:
+// the one-launch kernel, one workgroup per member slab). `workers` persistent workgroups take (member slab, step) tasks
+// from a bounded FIFO ring; ScreenArgs::cap then holds one capture slot per worker, not per member slab.
+struct QueueArgs {
+    unsigned long long* ring;    // [slots] (slots a power of two >= the launch's member slabs): sequence << 32 | task,
+                                 // task = member slab | (t + 1) << QUEUE_STEP_SHIFT
+    uint32_t* ctl;               // QUEUE_CTL_WORDS control words (below)
+    int32_t slots;
+    int32_t workers;             // workgroups of the launch (the grid is min(member slabs, workers))
+};
+#define QUEUE_STEP_SHIFT 20      // member slabs < 2^20, steps t + 1 < 2^12
+#define QUEUE_HEAD 0             // ctl: the ring's push position, the pop position and the finished member slabs, each on
+#define QUEUE_TAIL 32            // a 128-byte line of its own (set before every launch); then the counters that keep
+#define QUEUE_DONE 64            // counting over launches: tasks run, waits that ran past QUEUE_SPIN_TICKS
+#define QUEUE_GRID 65            // the launch's workers (each ends on one unfilled ticket: tail = head + workers)
+#define QUEUE_STEPS 96
+#define QUEUE_TIMEOUTS 97
+#define QUEUE_CTL_WORDS 128
+// the host's rules (pure: tests/test_step_queue_host.py through nicnes_decode_queue_plan)
+static inline int32_t nicnes_queue_ring_slots(int64_t items) {
+    int32_t n = 1;
+    while (n < items && n < (1 << QUEUE_STEP_SHIFT)) n <<= 1;
+    return n;
+}
+// mode 0 off, 1 on, 2 auto: more member slabs than workers (at or below, the one-launch kernel has every member slab
+// resident at once and nothing to level)
+static inline bool nicnes_queue_use(int mode, int64_t items, int workers) {
+    if (items < 1 || items > (1 << QUEUE_STEP_SHIFT) || workers < 1) return false;
+    return mode == 1 || (mode == 2 && items > workers);
+}
+
 // A mutated decode on the fused greedy path (mode != 0; the kernels' second argument, so the other kernels' argument
 // layout is untouched): the delta' rows in DecodeParams::noise hold only the parameters from off_log_w on (logit, i2h,
 // h2h: re-read at every step); the image projection and the embedding rows (read once, and only for the tokens taken)
@@ -125,7 +156,9 @@ extern "C" hipError_t nicnes_launch_decode_es(const DecodeParams* p, const Paren
 // mh: nullable (or mode 0): no decode-formed delta'
 extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead* mh, int member_count, int nslabs,
                                            hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch,
-                                           const ScreenArgs* sa = nullptr);   // sa: nullable (or cap NULL): the fp32 loop
+                                           const ScreenArgs* sa = nullptr,    // sa: nullable (or cap NULL): the fp32 loop
+                                           const QueueArgs* qa = nullptr);    // qa: nullable (or ring NULL): no step queue;
+                                                                              // else the screened decode runs from it
 // zero seq_logprobs past the batch's last finishing step (rollouts = members x 2 of B rows; after a
 // no_exit decode of a batch spanning several slabs)
 extern "C" hipError_t nicnes_launch_lp_batch_exit(const int32_t* seq, float* lp, int rollouts, int B, int T,

@@ -91,12 +91,24 @@ typedef __amdgpu_buffer_rsrc_t rsrc_t;
             q_[(stride) / 4 + (slot)] = (int32_t)(uint32_t)k_;                                   \
         }                                                                                        \
     } while (0)
+#if DECODE_PROF == 2
+// DECODE_PROF=2: the screened decode in its product launches (one launch, or the step queue's workers) with two marks
+// per workgroup, its start (slot 0) and end (slot 1), and none inside the steps (scripts/step_queue_spans.py)
+#define PROF_MARK(slot) do { } while (0)
+#define PROF_SPAN(slot) PROF_AT(blockIdx.x * gridDim.y + blockIdx.y, 4096, slot)
+#else
 #define PROF_MARK(slot) PROF_AT(blockIdx.x * gridDim.y + blockIdx.y, 4096, slot)
+#define PROF_SPAN(slot) do { } while (0)
+#endif
 #define PROF_SPLIT(slot) PROF_AT((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, 1024, slot)
 #else
 #define PROF_AT(wgi, stride, slot) do { } while (0)
 #define PROF_MARK(slot) do { } while (0)
+#define PROF_SPAN(slot) do { } while (0)
 #define PROF_SPLIT(slot) do { } while (0)
+#endif
+#ifndef DECODE_PROF_REVERSE
+#define DECODE_PROF_REVERSE 0   // DECODE_PROF=2 only: the one-launch screened kernel takes its members in reverse grid order
 #endif
 
 // lane id recomputed at the point of use (volatile: never hoisted or kept live across a loop)
@@ -122,6 +134,16 @@ __device__ __forceinline__ float ld1(rsrc_t r, uint32_t byte_off, uint32_t soff 
 }
 __device__ __forceinline__ void st1(rsrc_t r, uint32_t byte_off, uint32_t soff, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)byte_off, (int)soff, 0);
+}
+// the same with sc1 when HAND (write-through stores, loads past the L1: state handed to a workgroup on another CU, the
+// step queue's hand-off below); HAND false is ld1 / st1
+template <bool HAND>
+__device__ __forceinline__ float ld1h(rsrc_t r, uint32_t byte_off, uint32_t soff) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, (int)soff, HAND ? 16 : 0));
+}
+template <bool HAND>
+__device__ __forceinline__ void st1h(rsrc_t r, uint32_t byte_off, uint32_t soff, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)byte_off, (int)soff, HAND ? 16 : 0);
 }
 
 // ---- 32-row tiles (image projection, exact tie pass) ---------------------------------------
@@ -1716,6 +1738,31 @@ __device__ __forceinline__ Ctx make_ctx(const DecodeParams& p) {
     return c;
 }
 
+// the same for member slab wg = member * nslabs + slab of a launch whose workgroups are not its member slabs (the step
+// queue's workers); wg is wave-uniform
+__device__ __forceinline__ Ctx make_ctx_of(const DecodeParams& p, int wg, int nslabs) {
+    Ctx c;
+    c.tid = threadIdx.x;
+    c.lane = c.tid & 63;
+    c.wave = __builtin_amdgcn_readfirstlane(c.tid >> 6);
+    c.sgn = c.wave >> 2;
+    c.grp = c.wave & 3;
+    c.hh = c.lane >> 5;
+    c.member = wg / nslabs;
+    c.slab = wg - c.member * nslabs;
+    c.wg = wg;
+    c.b = c.slab * 128 + c.grp * 32 + (c.lane & 31);
+    c.row_valid = row_ok(p, c.b, c.sgn);
+    c.bc = c.row_valid ? c.b : 0;
+    const uint64_t nidx = p.noise_idx[c.member];
+    const uint32_t Dbytes = 4u * (uint32_t)p.D;
+    c.theta_r = make_rsrc(p.theta, Dbytes);
+    c.noise_r = make_rsrc(p.noise + nidx, Dbytes);
+    float* wscr = p.scratch + ((size_t)c.wg * 8 + c.wave) * (SCR_SLOTS * 64);
+    c.scr_r = make_rsrc(wscr, SCR_SLOTS * 64 * 4);
+    return c;
+}
+
 // ---- workgroup roles of the img kernel and the split path -----------------------------------
 // grid (q, member, slab). G = 4: wave w = sign (w >> 2) x 32-row group (w & 3) of a 128-row slab.
 // G = 2 (64-row slabs, B <= 64): wave w = sign (w >> 2) x group ((w >> 1) & 1) x tile half (w & 1);
@@ -1839,7 +1886,9 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_decode_img64_kernel(DecodePar
 // sample_pick draws each row's token with its uniform p.sample_u (fused path only)
 // SCREEN (PAIRS, greedy only): the logit loop runs in bf16 and the candidates it leaves are certified on fp32
 // MFMA tiles (ScreenStage / screen_scan / certify_tiles above); tokens are those of the fp32 loop
-template <bool PAIRS, bool PREFETCH, bool SAMPLE = false, bool MUT = false, bool SCREEN = false>
+// QUEUE (SCREEN only; the step queue's workers): the capture slot is the worker's (blockIdx.x), not the member slab's: it
+// is written and read within one step, so a worker needs one whatever member slab it runs
+template <bool PAIRS, bool PREFETCH, bool SAMPLE = false, bool MUT = false, bool SCREEN = false, bool QUEUE = false>
 __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, float* lds, int t, Stage64Regs& s64,
                                           bool& pre, float (&hB)[64], bool& hpre, const MutRes* mr = nullptr,
                                           const ScreenArgs* sa = nullptr) {
@@ -1849,7 +1898,7 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
     const int nl = t > 0 ? nst : 0;
     const uint64_t nidx = p.noise_idx[c.member];
     // the row's unfinished flag, read now: the token phase needs it right after the logit loop
-    const float unf_prev = nl > 0 ? ld1(c.scr_r, lo, U_SLOT) : 0.f;
+    const float unf_prev = nl > 0 ? ld1h<QUEUE>(c.scr_r, lo, U_SLOT) : 0.f;
     // SAMPLE: the row's uniform for this step, loaded now (the pick's first dependent load otherwise)
     double u_pre = 0.5;
     if constexpr (SAMPLE) {
@@ -1861,7 +1910,7 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
         for (int i = 0; i < 64; ++i) hB[i] = 0.f;               // h = 0 before the first cell
     } else if (!hpre) {                                          // (hpre: loaded at the end of the last step)
 #pragma unroll
-        for (int i = 0; i < 64; ++i) hB[i] = ld1(c.scr_r, lo, H_SLOT(i));
+        for (int i = 0; i < 64; ++i) hB[i] = ld1h<QUEUE>(c.scr_r, lo, H_SLOT(i));
     }
     hpre = false;
 #pragma unroll
@@ -1886,7 +1935,8 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
         float seps = 0.f;                          // SCREEN: the row's eps
         rsrc_t scap_r = c.scr_r;                   // SCREEN: the workgroup's capture slot
         if constexpr (SCREEN)
-            scap_r = make_rsrc(sa->cap + (size_t)c.wg * SCREEN_CAP_WORDS(p.V1), 4u * (uint32_t)SCREEN_CAP_WORDS(p.V1));
+            scap_r = make_rsrc(sa->cap + (size_t)(QUEUE ? (int)blockIdx.x : c.wg) * SCREEN_CAP_WORDS(p.V1),
+                               4u * (uint32_t)SCREEN_CAP_WORDS(p.V1));
         // the cell's first gate tile does not depend on the token: its loads are issued at the last logit
         // stage's mid-point (tail) and land while the token is picked
         const bool xpre = t < p.T;
@@ -2119,7 +2169,7 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
         // finished mask (nets.py:236-243); forward_for_sensitivity feeds every argmax back (nets.py:62-63)
         const bool unfinished = unf_prev != 0.f && tok > 0;
         it = (unfinished || p.no_mask) ? tok : 0;
-        st1(c.scr_r, lo, U_SLOT, unfinished ? 1.f : 0.f);
+        st1h<QUEUE>(c.scr_r, lo, U_SLOT, unfinished ? 1.f : 0.f);
 #if !DECODE_PROF
         if (c.hh == 0 && c.row_valid) {
             const size_t o = (((size_t)c.member * 2 + c.sgn) * p.B + c.b) * p.T + (t - 1);
@@ -2183,20 +2233,20 @@ __device__ __forceinline__ bool step_body(const DecodeParams& p, const Ctx& c, f
             for (int r = 0; r < 16; ++r) {
                 const float fcv = CELL_SIG(s_[r]) * cpre[r];
                 const float cn = fcv + hold[r];
-                st1(c.scr_r, lo_, C_SLOT(16 * U + r), cn);
+                st1h<QUEUE>(c.scr_r, lo_, C_SLOT(16 * U + r), cn);
                 hold[r] = cn;
             }
         } else {                                                 // h' = o * tanh(c')
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                st1(c.scr_r, lo_, H_SLOT(16 * U + r), CELL_SIG(s_[r]) * CELL_TANH(hold[r]));
+                st1h<QUEUE>(c.scr_r, lo_, H_SLOT(16 * U + r), CELL_SIG(s_[r]) * CELL_TANH(hold[r]));
         }
     };
     auto load_c = [&](int m) __attribute__((always_inline)) {                                   // c of the f tile's unit block
         f32x16 cp;
         const uint32_t lo_ = 4u * (uint32_t)lane_fresh();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) cp[r] = (m % 5 == 3 && t >= 0) ? ld1(c.scr_r, lo_, C_SLOT(16 * (m / 5) + r)) : 0.f;
+        for (int r = 0; r < 16; ++r) cp[r] = (m % 5 == 3 && t >= 0) ? ld1h<QUEUE>(c.scr_r, lo_, C_SLOT(16 * (m / 5) + r)) : 0.f;
         return cp;
     };
 #pragma unroll 1
@@ -2346,12 +2396,147 @@ __global__ __launch_bounds__(NTHREADS) void nicnes_decode_steps_kernel(DecodePar
 // the screened greedy-only decode on the fused path (step_body SCREEN; ScreenArgs)
 __global__ __launch_bounds__(NTHREADS) void nicnes_decode_steps_screen_kernel(DecodeParams p, ScreenArgs sa) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+#if DECODE_PROF == 2 && DECODE_PROF_REVERSE
+    const Ctx c = make_ctx_of(p, (int)(gridDim.x * gridDim.y - 1 - (blockIdx.x * gridDim.y + blockIdx.y)), (int)gridDim.y);
+#else
     const Ctx c = make_ctx(p);
+#endif
+    PROF_SPAN(0);
     Stage64Regs s64;
     bool pre = false, hpre = false;
     float hB[64];
     for (int t = -1; t <= p.T; ++t)
         if (!step_body<true, true, false, false, true>(p, c, lds, t, s64, pre, hB, hpre, nullptr, &sa)) break;
+    PROF_SPAN(1);
+}
+
+// ---- the step queue -----------------------------------------------------------------------------------------------
+// The screened decode above with (member slab, step) as the unit of dispatch instead of the member slab. One workgroup
+// is resident per CU (LDS), so a launch of more member slabs than CUs runs them back to back, and it lasts as long as
+// the CU with the largest sum: the CUs that finish early stand idle ("Step queue"). Here min(member slabs,
+// workers) persistent workgroups take tasks from a FIFO ring: a worker pops a member slab with its step t, runs that
+// one step (step_body, the state between steps being the member slab's lane scratch, as in the DECODE_PROF build's one
+// launch per step), and pushes the member slab back with t + 1 unless it has finished. First in, first out keeps every
+// chain advancing together, so the launch ends within about one step of total work / workers. A step is a pure
+// function of the member slab's scratch, theta, its noise slice and the batch: tokens do not depend on who runs it.
+//
+// The ring (sequence words as in D. Vyukov's bounded MPMC queue, positions claimed by fetch-and-add): `slots` 64-bit
+// words, sequence << 32 | task, written and read whole by agent-scope atomics, so a task is never seen without its
+// sequence. Slot i starts at sequence i (free for the push at position i). A push takes its position q from the head by
+// a fetch-and-add, waits until the slot reads q (free) and leaves q + 1 with the task; a pop takes its ticket q from the
+// tail the same way, waits for q + 1, and leaves q + slots for the push a lap later. A pop therefore never reads a slot
+// before its push has landed, and a push that has wrapped round never overwrites a slot whose popper has not left it:
+// nothing rests on how long a step takes. (Not claimed by compare-and-swap as in the original: the workers end their
+// steps at about the same time and would retry against each other.) A ticket beyond the
+// last push is never filled: its holder leaves once every member slab is counted finished, and that is how every
+// worker ends, with one unfilled ticket each (tail = head + workers after a sound launch). If every worker waits on a
+// ticket, no task is in the ring (tickets and positions are both dense) and none is running, so all have finished.
+// nicnes_queue_init_kernel, the launch before on the same stream, fills the ring with every member slab at t = -1 and
+// sets head, tail and the finished count.
+// Only thread 0 pops, polls and pushes (relaxed agent-scope atomics, s_sleep between polls); the workgroup learns the
+// task through LDS and a barrier, as coop_wait's callers do.
+// No co-residency is needed: a worker that finds the ring empty while member slabs remain unfinished waits only for the
+// pushes of workers that are running a step at that moment (a task is either in the ring or being run; a running step
+// ends without waiting for anyone), so a worker that has not started yet is never waited for. Every wait is bounded by
+// QUEUE_SPIN_TICKS all the same: past it the worker leaves, ctl[QUEUE_TIMEOUTS] and stats[2] count it, and the engine
+// reports the evaluate as faulted, as for the coop path's hand-off timeout.
+// Hand-off of a member slab's scratch (written on one CU, read on another, maybe on another XCD; MI355X_MICROARCH.md,
+// inter-workgroup visibility: the sc1 form, as coop_arrive / coop_wait<false> below). Producer: the step's stores of
+// U_SLOT, C_SLOT and H_SLOT all sc1 (st1h: write-through) -> every wave's s_waitcnt vmcnt(0) -> barrier -> thread 0's
+// push (an sc1 store of the slot word). Consumer: thread 0's poll of the slot word (an sc1 load) -> barrier -> every load
+// of U_SLOT, H_SLOT and C_SLOT sc1 (ld1h: past the L1). One workgroup per CU (LDS), hipMalloc memory, 4-byte accesses.
+// (The form with an agent release fence before the push and an agent acquire after the pop passes the same tests; it
+// writes back the XCD's whole L2 once per step and worker.) X_SLOT is the launch before's; p.alive and seq are only written here (read after
+// the launch); the step travels in the task word; the finished count and the counters are agent-scope atomics.
+#define QUEUE_SPIN_TICKS 50000000ull     // 0.5 s of s_memrealtime (100 MHz), as COOP_SPIN_TICKS
+
+__global__ __launch_bounds__(256) void nicnes_queue_init_kernel(QueueArgs qa, int items, int grid) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < qa.slots; i += gridDim.x * blockDim.x)
+        qa.ring[i] = i < items ? ((unsigned long long)(uint32_t)(i + 1) << 32) | (uint32_t)i
+                               : (unsigned long long)(uint32_t)i << 32;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        qa.ctl[QUEUE_HEAD] = (uint32_t)items;
+        qa.ctl[QUEUE_TAIL] = 0u;
+        qa.ctl[QUEUE_DONE] = 0u;
+        qa.ctl[QUEUE_GRID] = (uint32_t)grid;
+    }
+}
+
+#define QLOAD(ptr) __hip_atomic_load(ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+// thread 0: the next task; -1 when every member slab has finished, -2 when the wait ran past its bound
+__device__ __forceinline__ int queue_pop(const QueueArgs& qa, int items) {
+    const uint32_t mask = (uint32_t)qa.slots - 1u;
+    const uint32_t pos = __hip_atomic_fetch_add(qa.ctl + QUEUE_TAIL, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    for (;;) {
+        const unsigned long long w = QLOAD(qa.ring + (pos & mask));
+        if ((uint32_t)(w >> 32) == pos + 1u) {
+            __hip_atomic_store(qa.ring + (pos & mask), (unsigned long long)(pos + mask + 1u) << 32, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+            return (int)(uint32_t)w;
+        }
+        // no push at pos has landed yet
+        if (QLOAD(qa.ctl + QUEUE_DONE) >= (uint32_t)items) return -1;
+        __builtin_amdgcn_s_sleep(8);
+        if (__builtin_amdgcn_s_memrealtime() - t0 > QUEUE_SPIN_TICKS) return -2;
+    }
+}
+
+// thread 0: false when the slot stayed taken past the bound (the popper of a lap ago never left it)
+__device__ __forceinline__ bool queue_push(const QueueArgs& qa, uint32_t task) {
+    const uint32_t mask = (uint32_t)qa.slots - 1u;
+    const uint32_t pos = __hip_atomic_fetch_add(qa.ctl + QUEUE_HEAD, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    while ((uint32_t)(QLOAD(qa.ring + (pos & mask)) >> 32) != pos) {
+        __builtin_amdgcn_s_sleep(8);
+        if (__builtin_amdgcn_s_memrealtime() - t0 > QUEUE_SPIN_TICKS) return false;
+    }
+    __hip_atomic_store(qa.ring + (pos & mask), ((unsigned long long)(pos + 1u) << 32) | task, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+    return true;
+}
+#undef QLOAD
+
+__global__ __launch_bounds__(NTHREADS) void nicnes_decode_steps_screen_queue_kernel(DecodeParams p, ScreenArgs sa,
+                                                                                    QueueArgs qa, int items, int nslabs) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ int task_sh;
+    PROF_SPAN(0);
+    bool dead = false;                                 // thread 0: a wait of this worker ran past its bound
+    for (;;) {
+        if (threadIdx.x == 0) {
+            const int task = dead ? -2 : queue_pop(qa, items);
+            if (task == -2 && !dead) {
+                __hip_atomic_fetch_add(qa.ctl + QUEUE_TIMEOUTS, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                atomicAdd(p.stats + 2, 1);
+            }
+            task_sh = task;
+        }
+        __syncthreads();                               // (the other waves load behind the barrier the polling wave joins)
+        const int task = __builtin_amdgcn_readfirstlane(task_sh);
+        if (task < 0) break;
+        const int wg = task & ((1 << QUEUE_STEP_SHIFT) - 1), t = (task >> QUEUE_STEP_SHIFT) - 1;
+        const Ctx c = make_ctx_of(p, wg, nslabs);
+        Stage64Regs s64;
+        bool pre = false, hpre = false;
+        float hB[64];
+        const bool more = step_body<true, false, false, false, true, true>(p, c, lds, t, s64, pre, hB, hpre, nullptr, &sa);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's stores of the step have landed
+        __syncthreads();                                     // (also: every thread has read task_sh)
+        if (threadIdx.x == 0) {
+            __hip_atomic_fetch_add(qa.ctl + QUEUE_STEPS, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (more) {
+                if (!queue_push(qa, (uint32_t)wg | ((uint32_t)(t + 2) << QUEUE_STEP_SHIFT))) {
+                    dead = true;
+                    __hip_atomic_fetch_add(qa.ctl + QUEUE_TIMEOUTS, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    atomicAdd(p.stats + 2, 1);
+                }
+            } else {
+                __hip_atomic_fetch_add(qa.ctl + QUEUE_DONE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+    PROF_SPAN(1);
 }
 
 // a mutated greedy decode on the fused path (MutHead: the embedding rows' delta' formed in step_body)
@@ -3259,6 +3444,7 @@ extern "C" hipError_t nicnes_decode_init() {
         {(const void*)nicnes_decode_steps_kernel<false>, LDS64},
         {(const void*)nicnes_decode_steps_kernel<false, true>, LDS64},
         {(const void*)nicnes_decode_steps_screen_kernel, LDS_SCREEN},
+        {(const void*)nicnes_decode_steps_screen_queue_kernel, LDS_SCREEN},
         {(const void*)nicnes_decode_steps_mut_kernel<true>, LDS64},
         {(const void*)nicnes_decode_steps_mut_kernel<false>, LDS64},
         {(const void*)nicnes_decode_img64_es_kernel, LDS64},
@@ -3332,7 +3518,7 @@ extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead
 
 extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead* mh, int member_count, int nslabs,
                                            hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch,
-                                           const ScreenArgs* sa) {
+                                           const ScreenArgs* sa, const QueueArgs* qa) {
     const bool fused = p->G == 4 && p->S == 1;
     if (p->G != 4 && p->G != 2) return hipErrorInvalidValue;
     if (p->S < 1 || p->S > 64) return hipErrorInvalidValue;
@@ -3389,10 +3575,19 @@ extern "C" hipError_t nicnes_launch_decode(const DecodeParams* p, const MutHead*
             hipLaunchKernelGGL((nicnes_decode_steps_kernel<false, true>), grid, block, LDS64, stream, *p);
             mark(DK_STEPS);
         } else {
-#if !DECODE_PROF
+#if DECODE_PROF != 1
             if (!mut && pairs && sa && sa->cap && sa->norm) {
                 hipLaunchKernelGGL(nicnes_screen_norm_kernel, dim3(member_count), block, 0, stream, *p, *sa);
-                hipLaunchKernelGGL(nicnes_decode_steps_screen_kernel, grid, block, LDS_SCREEN, stream, *p, *sa);
+                const int items = member_count * nslabs;
+                if (qa && qa->ring && qa->workers > 0 && items <= qa->slots) {
+                    // the step queue: the ring refilled on the same stream, then min(member slabs, workers) workers
+                    const int nw = items < qa->workers ? items : qa->workers;
+                    hipLaunchKernelGGL(nicnes_queue_init_kernel, dim3((qa->slots + 255) / 256), dim3(256), 0, stream, *qa, items, nw);
+                    hipLaunchKernelGGL(nicnes_decode_steps_screen_queue_kernel, dim3(nw),
+                                       block, LDS_SCREEN, stream, *p, *sa, *qa, items, nslabs);
+                } else {
+                    hipLaunchKernelGGL(nicnes_decode_steps_screen_kernel, grid, block, LDS_SCREEN, stream, *p, *sa);
+                }
             } else if (mut && pairs)
                 hipLaunchKernelGGL(nicnes_decode_steps_mut_kernel<true>, grid, block, LDS64, stream, *p, *mh);
             else if (mut)

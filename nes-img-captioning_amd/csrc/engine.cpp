@@ -177,6 +177,11 @@ struct nicnes_handle {
     float* screen_norm = nullptr;      // [max_members][4]
     unsigned long long* screen_ctr = nullptr;   // [SCREEN_CTR_WORDS] (ScreenArgs::ctr)
     int screen_rounds = SCREEN_ROUNDS_DEFAULT;  // NICNES_SCREEN_ROUNDS: certify rounds of an over-cap lane (ScreenArgs::rounds)
+    int queue_mode = 2;                // NICNES_DECODE_QUEUE / nicnes_set_decode_queue: the screened decode's step queue
+    int queue_workers = 0;             // NICNES_DECODE_QUEUE_WORKERS: its workers (0: one per CU)
+    unsigned long long* queue_ring = nullptr;   // [queue_slots] (QueueArgs::ring; allocated with the screening buffers)
+    uint32_t* queue_ctl = nullptr;     // [QUEUE_CTL_WORDS]
+    int32_t queue_slots = 0;
     int exact_left = 0;
     int last_bounded = 0;
     int last_decode_bounded = 0;      // nicnes_last_decode_lse: the lse mode of the last decode enqueued
@@ -372,6 +377,15 @@ void decode_shape(const nicnes_handle* h, int B, int count, int* G, int* nslabs,
 
 // The coop path (the split shape in one persistent launch, nicnes_decode_coop_kernel): 128-row slabs, 2 or
 // 4 logit ranges per member slab, and every workgroup of the launch resident at once (one per CU).
+// the step queue's switch from the environment: NICNES_DECODE_QUEUE=0/1/2 and NICNES_DECODE_QUEUE_WORKERS=n (n >= 1; anything
+// else leaves the value as it is)
+void queue_env(int* mode, int* workers) {
+    const char* dq = getenv("NICNES_DECODE_QUEUE");
+    if (dq && dq[0] >= '0' && dq[0] <= '2' && dq[1] == 0) *mode = dq[0] - '0';
+    const char* dw = getenv("NICNES_DECODE_QUEUE_WORKERS");
+    if (dw && dw[0] && atoi(dw) >= 1) *workers = atoi(dw);
+}
+
 bool coop_fits(const nicnes_handle* h, int G, int nslabs, int S, int count) {
     // (nst >= S: coop_step assumes every logit range non-empty; the split path handles empty ranges)
     return h->coop_mode && G == 4 && (S == 2 || S == 4) && (h->V1 + 63) / 64 >= S &&
@@ -389,15 +403,28 @@ void ensure_screen(nicnes_handle* h) {
     if (ok && !h->screen_ctr)
         ok = hipMalloc((void**)&h->screen_ctr, SCREEN_CTR_WORDS * sizeof(unsigned long long)) == hipSuccess &&
              hipMemset(h->screen_ctr, 0, SCREEN_CTR_WORDS * sizeof(unsigned long long)) == hipSuccess;
+    // the step queue's ring (a slot per member slab of the largest fused decode, rounded up to a power of two) and its
+    // control words
+    const int32_t slots = nicnes_queue_ring_slots(wgs);
+    if (ok && !h->queue_ring && slots >= wgs)
+        ok = hipMalloc((void**)&h->queue_ring, (size_t)slots * sizeof(unsigned long long)) == hipSuccess &&
+             hipMalloc((void**)&h->queue_ctl, QUEUE_CTL_WORDS * sizeof(uint32_t)) == hipSuccess &&
+             hipMemset(h->queue_ctl, 0, QUEUE_CTL_WORDS * sizeof(uint32_t)) == hipSuccess;
     if (ok) {
         h->screen_wgs = wgs;
+        if (h->queue_ring) h->queue_slots = slots;
         return;
     }
     (void)hipGetLastError();
     if (h->screen_cap) (void)hipFree(h->screen_cap);
     if (h->screen_norm) (void)hipFree(h->screen_norm);
+    if (h->queue_ring) (void)hipFree(h->queue_ring);
+    if (h->queue_ctl) (void)hipFree(h->queue_ctl);
     h->screen_cap = nullptr;
     h->screen_norm = nullptr;
+    h->queue_ring = nullptr;
+    h->queue_ctl = nullptr;
+    h->queue_slots = 0;
     h->screen_mode = 0;
 }
 
@@ -537,6 +564,7 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
         if (se && se[0]) h->screen_scale = std::max(1.0f, (float)atof(se));
         const char* sr = getenv("NICNES_SCREEN_ROUNDS");
         if (sr && sr[0]) h->screen_rounds = std::min(SCREEN_ROUNDS_MAX, std::max(1, atoi(sr)));
+        queue_env(&h->queue_mode, &h->queue_workers);
     }
     {
         int ncu = 0;
@@ -603,7 +631,7 @@ int nicnes_destroy(nicnes_handle* h) {
                     h->hash_keys, h->hash_vals, h->img_hkey, h->img_hrow, h->img_vr, h->alive, h->part,
                     h->rank_key, h->rank_idx, h->mbatch, h->mut_vec, h->dbuf, h->didx, h->noise_sc, h->coop_ctr,
                     h->zero_noise, h->zero_idx, h->sens_tok, h->su, h->base_scores, h->slog, h->slog_slots, h->zcount,
-                    h->screen_cap, h->screen_norm, h->screen_ctr, h->dr_fc, h->dr_refs, h->dr_start, h->dr_stage};
+                    h->screen_cap, h->screen_norm, h->screen_ctr, h->queue_ring, h->queue_ctl, h->dr_fc, h->dr_refs, h->dr_start, h->dr_stage};
     if (h->sens) nicnes_sens_destroy(h->sens);
     for (void* p : bufs)
         if (p) (void)hipFree(p);
@@ -1206,7 +1234,7 @@ static int score_rollouts(nicnes_handle* h, const int32_t* seq, const float* lp,
 // The decode of `count` members enqueued on s, or in parts on s and the engine's streams (the one launch sequence of
 // nicnes_evaluate* and nicnes_split_decode). Returns the number of streams used, or -(error code).
 static int launch_decode_parts(nicnes_handle* h, const DecodeParams& p, const MutHead& mh, const ScreenArgs& sa, int count,
-                               int nslabs, hipStream_t s, bool timed, int* n_ev) {
+                               int nslabs, hipStream_t s, bool timed, int* n_ev, const QueueArgs* qa = nullptr) {
 #define HIPN(expr)                                                                                           \
     do {                                                                                                     \
         hipError_t e_ = (expr);                                                                              \
@@ -1239,7 +1267,8 @@ static int launch_decode_parts(nicnes_handle* h, const DecodeParams& p, const Mu
             HIPN(hipStreamWaitEvent(s, h->ev_join[i], 0));
         }
     } else {
-        HIPN(nicnes_launch_decode(&p, &mh, count, nslabs, s, timed ? h->dev : nullptr, h->dev_kind, n_ev, &sa));
+        // (the step queue: only a decode in one part; the parts of a decode over several streams would share its ring)
+        HIPN(nicnes_launch_decode(&p, &mh, count, nslabs, s, timed ? h->dev : nullptr, h->dev_kind, n_ev, &sa, qa));
     }
 #undef HIPN
     return nstr;
@@ -1421,6 +1450,14 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
             sa.norm = h->screen_norm;
         }
     }
+    // the screened decode from the step queue: more member slabs than workers (automatic), or forced on
+    QueueArgs qa{nullptr, nullptr, 0, 0};
+    {
+        const int workers = h->queue_workers > 0 ? h->queue_workers : h->n_cu;
+        if (sa.cap && h->queue_ring && (int64_t)count * nslabs <= h->queue_slots &&
+            nicnes_queue_use(h->queue_mode, (int64_t)count * nslabs, workers))
+            qa = QueueArgs{h->queue_ring, h->queue_ctl, h->queue_slots, workers};
+    }
     p.G = G;
     p.S = S;
     p.part = h->part;
@@ -1469,7 +1506,7 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     if (p.lp) HIPC(h, hipMemsetAsync(p.lp, 0, out_rows * h->cfg.seq_length * sizeof(float), s));
     if (h->timing) HIPC(h, hipEventRecord(h->ev[0], s));
     int n_ev = 0;
-    const int nstr = launch_decode_parts(h, p, mh, sa, count, nslabs, s, h->timing, &n_ev);
+    const int nstr = launch_decode_parts(h, p, mh, sa, count, nslabs, s, h->timing, &n_ev, &qa);
     if (nstr < 0) return -nstr;
     h->n_dev = h->timing ? n_ev : 0;
     h->multi_stream = nstr > 1;
@@ -2038,12 +2075,40 @@ int nicnes_optimizer_update(nicnes_handle* h, int kind, const double* globalg, i
     return opt_step(h, kind, nullptr, 0, 0.0, globalg, globalg_fp32, stepsize, beta1, beta2, epsilon, ratio_out_host, stream);
 }
 
-int nicnes_stats(nicnes_handle* h, int64_t* out4_host) {
-    if (!h || !out4_host) return NICNES_ERR_INVALID;
+int nicnes_stats(nicnes_handle* h, int64_t* out8_host) {
+    if (!h || !out8_host) return NICNES_ERR_INVALID;
     int32_t st[4];
     HIPC(h, hipSetDevice(h->device));
     HIPC(h, hipMemcpy(st, h->stats, sizeof st, hipMemcpyDeviceToHost));
-    for (int i = 0; i < 4; ++i) out4_host[i] = st[i];
+    for (int i = 0; i < 4; ++i) out8_host[i] = st[i];
+    // the step queue: tasks run and timeouts (over the handle's life), then the state the last queue launch left: member
+    // slabs finished, tasks still in the ring
+    uint32_t q[QUEUE_CTL_WORDS] = {0};
+    if (h->queue_ctl) HIPC(h, hipMemcpy(q, h->queue_ctl, sizeof q, hipMemcpyDeviceToHost));
+    out8_host[4] = q[QUEUE_STEPS];
+    out8_host[5] = q[QUEUE_TIMEOUTS];
+    out8_host[6] = q[QUEUE_DONE];
+    out8_host[7] = (int64_t)(int32_t)(q[QUEUE_HEAD] + q[QUEUE_GRID] - q[QUEUE_TAIL]);   // (each worker ends on an unfilled ticket)
+    return NICNES_OK;
+}
+
+int nicnes_set_decode_queue(nicnes_handle* h, int32_t mode, int32_t workers) {
+    if (!h || mode < 0 || mode > 2 || workers < 0) return NICNES_ERR_INVALID;
+    h->queue_mode = mode;
+    h->queue_workers = workers;
+    return NICNES_OK;
+}
+
+int nicnes_decode_queue_plan(int32_t mode, int32_t workers, int32_t n_cu, int32_t members, int32_t slabs,
+                             int32_t* out3_host) {
+    if (!out3_host || n_cu < 1 || members < 1 || slabs < 1 || mode > 2 || workers < 0) return NICNES_ERR_INVALID;
+    int m = mode < 0 ? 2 : mode, w = workers;
+    if (mode < 0) queue_env(&m, &w);
+    if (w < 1) w = n_cu;
+    const int64_t items = (int64_t)members * slabs;
+    out3_host[0] = nicnes_queue_use(m, items, w) ? 1 : 0;
+    out3_host[1] = (int32_t)std::min<int64_t>(items, w);
+    out3_host[2] = nicnes_queue_ring_slots(items);
     return NICNES_OK;
 }
 

@@ -25,7 +25,7 @@ EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_create', 'nicne
            'nicnes_evaluate_theta', 'nicnes_set_sample_draws', 'nicnes_set_rows_per_image',
            'nicnes_last_decode_lse', 'nicnes_test_logit_chain', 'nicnes_test_score_rows',
            'nicnes_test_certify_items', 'nicnes_test_certify_items_owned',
-           'nicnes_set_decode_screen', 'nicnes_screen_stats', 'nicnes_screen_reasons', 'nicnes_split_create', 'nicnes_split_destroy',
+           'nicnes_set_decode_screen', 'nicnes_set_decode_queue', 'nicnes_decode_queue_plan', 'nicnes_screen_stats', 'nicnes_screen_reasons', 'nicnes_split_create', 'nicnes_split_destroy',
            'nicnes_split_decode', 'nicnes_split_score', 'nicnes_split_evaluate',
            'nicnes_es_create', 'nicnes_es_free', 'nicnes_es_set_mutation', 'nicnes_es_set_parent',
            'nicnes_es_set_parent_count', 'nicnes_es_get_row', 'nicnes_es_row_stats', 'nicnes_es_evaluate',
@@ -107,6 +107,8 @@ def lib(path=None):
         'nicnes_decode_path': (c.c_int, [vp, i32, i32, vp]),
         'nicnes_last_decode_lse': (c.c_int, [vp, vp]),
         'nicnes_set_decode_screen': (c.c_int, [vp, i32]),
+        'nicnes_set_decode_queue': (c.c_int, [vp, i32, i32]),
+        'nicnes_decode_queue_plan': (c.c_int, [i32, i32, i32, i32, i32, vp]),
         'nicnes_screen_stats': (c.c_int, [vp, vp]),
         'nicnes_screen_reasons': (c.c_int, [vp, vp]),
         'nicnes_test_logit_chain': (c.c_int, [vp, u64, i32, f32, i32, vp, vp, vp, vp]),

@@ -36,6 +36,17 @@ def df_table_arrays(document_frequency):
     return keys, vals
 
 
+def decode_queue_plan(members, slabs=1, n_cu=256, mode=None, workers=0):
+    """(queue kernel runs, its workgroups, ring slots) of a screened fused decode of members x slabs member slabs
+    (nicnes_decode_queue_plan; needs no GPU). mode None: mode and workers from NICNES_DECODE_QUEUE[_WORKERS]."""
+    from ._lib import lib
+    out = (ctypes.c_int32 * 3)()
+    m = -1 if mode is None else (2 if mode == 'auto' else int(mode))
+    check(lib().nicnes_decode_queue_plan(m, int(workers), int(n_cu), int(members), int(slabs), out), None,
+          'decode_queue_plan')
+    return bool(out[0]), int(out[1]), int(out[2])
+
+
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
@@ -463,6 +474,12 @@ class Engine:
         mode = 2 if (isinstance(on, str) and on == 'auto') else int(bool(on))
         check(self.L.nicnes_set_decode_screen(self.h, mode), self.h, 'set_decode_screen')
 
+    def set_decode_queue(self, mode='auto', workers=0):
+        """The screened decode's step queue on (True), off (False) or 'auto' (the default: on when the decode has more
+        member slabs than workers); workers 0: one per CU. Tokens do not depend on it."""
+        m = 2 if (isinstance(mode, str) and mode == 'auto') else int(bool(mode))
+        check(self.L.nicnes_set_decode_queue(self.h, m, int(workers)), self.h, 'set_decode_queue')
+
     def test_logit_chain(self, iteration, member, sigma, sign, h_rows):
         """Test entry: the logits of one (member, sign) over h_rows [32, 128] by the exact pass's MFMA tile path and by
         the fmaf chain in the MFMA's k order; two [32, vocab_size + 1] fp32 tensors, equal bit for bit."""
@@ -727,7 +744,7 @@ class Engine:
         return {'coop_timeouts': int(out[0]), 'sample_slot_timeouts': int(out[1])}
 
     def stats(self):
-        out = (ctypes.c_int64 * 4)()
+        out = (ctypes.c_int64 * 8)()
         check(self.L.nicnes_stats(self.h, out), self.h, 'stats')
         sc = (ctypes.c_int64 * 2)()
         check(self.L.nicnes_screen_stats(self.h, sc), self.h, 'screen_stats')
@@ -737,7 +754,8 @@ class Engine:
              'sample_slot_timeouts': out[3], 'screen_candidates': sc[0], 'screen_fallback_rows': sc[1],
              'screen_rows_over_cap': sr[0], 'screen_rows_undecided': sr[1], 'screen_rows_evicted': sr[2],
              'screen_rows_nonfinite': sr[3], 'screen_rows_settled_later': sr[4], 'screen_resweep_rows': sr[5],
-             'screen_resweep_steps': sr[6], 'screen_resweep_waves': sr[15]}
+             'screen_resweep_steps': sr[6], 'screen_resweep_waves': sr[15],
+             'queue_steps': out[4], 'queue_timeouts': out[5], 'queue_finished': out[6], 'queue_pending': out[7]}
         # over-cap rows by the certify rounds their fuller lane needs at least (the last: 9 or more); plain integers,
         # so that callers can subtract two stats() key by key
         d.update({'screen_over_cap_rounds_%d' % (k + 2): sr[7 + k] for k in range(8)})
