@@ -1510,7 +1510,9 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     if (nstr < 0) return -nstr;
     h->n_dev = h->timing ? n_ev : 0;
     h->multi_stream = nstr > 1;
-    if (p.no_exit)    // eval_theta: the two halves are one rollout
+    // also with one slab: its workgroup holds both signs and runs until the later of the two has finished, writing the
+    // earlier one's log-probs past that rollout's own last step (eval_theta: the two halves are one rollout)
+    if (p.lp)
         HIPC(h, nicnes_launch_lp_batch_exit(p.seq, p.lp, eval_theta ? 1 : 2 * count, rows_total, h->cfg.seq_length, s));
     if (h->timing) HIPC(h, hipEventRecord(h->ev[1], s));
     if (!h->stats_pending) {          // read the fallback counter back without a host wait
@@ -2952,7 +2954,7 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
     }
     h->n_dev = 0;
     h->multi_stream = nstr > 1;
-    if (p.no_exit) HIPC(h, nicnes_launch_lp_batch_exit(p.seq, p.lp, 2 * count, rows, h->cfg.seq_length, s));
+    if (p.lp) HIPC(h, nicnes_launch_lp_batch_exit(p.seq, p.lp, 2 * count, rows, h->cfg.seq_length, s));   // (as evaluate_impl)
     if (h->timing) HIPC(h, hipEventRecord(h->ev[1], s));
     if (!h->stats_pending) {
         HIPC(h, hipMemcpyAsync(h->stats_host, h->stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));

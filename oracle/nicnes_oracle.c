@@ -135,9 +135,9 @@ static int greedy_pick(const float* logits, int V1, float* lp_out, uint8_t* frag
  * sum(p) in fp32 (np.linalg.norm(row, ord=1)), then RandomState.choice(len, 1, p=n): cdf = cumsum(n)
  * in fp64 divided by its last entry, pick = first index with cdf > u (searchsorted side='right').
  * lp = the pick's log-prob (logprobs.gather). fragile = u within 1e-6 of the cdf boundary below or at
- * the pick (a different summation order of p moves the boundaries by ~1e-7). pbuf/cdf: [V1] scratch. */
-static int sample_pick(const float* logits, int V1, double u, float* pbuf, double* cdf, float* lp_out,
-                       uint8_t* fragile) {
+ * the pick (a different summation order of p moves the boundaries by ~1e-7). pbuf/cdf: [V1] scratch.
+ * sample_cdf forms the (unnormalised) cdf, the row maximum and lse; sample_pick and planted_pick share it. */
+static void sample_cdf(const float* logits, int V1, float* pbuf, double* cdf, float* m_out, float* lse_out) {
     float m = logits[0];
     for (int v = 1; v < V1; ++v) if (logits[v] > m) m = logits[v];
     double s = 0.0;
@@ -148,6 +148,14 @@ static int sample_pick(const float* logits, int V1, double u, float* pbuf, doubl
     const float normf = (float)norm;
     double c = 0.0;
     for (int v = 0; v < V1; ++v) { c += (double)(pbuf[v] / normf); cdf[v] = c; }
+    *m_out = m;
+    *lse_out = lse;
+}
+
+static int sample_pick(const float* logits, int V1, double u, float* pbuf, double* cdf, float* lp_out,
+                       uint8_t* fragile) {
+    float m, lse;
+    sample_cdf(logits, V1, pbuf, cdf, &m, &lse);
     const double last = cdf[V1 - 1];
     int tok = V1 - 1;
     for (int v = 0; v < V1; ++v) if (cdf[v] / last > u) { tok = v; break; }
@@ -157,8 +165,28 @@ static int sample_pick(const float* logits, int V1, double u, float* pbuf, doubl
     return tok;
 }
 
+/* planted pick: the cdf of sample_pick, the draw aimed at id tgt: *u_out = the midpoint of tgt's interval
+ * [cdf[tgt-1], cdf[tgt]) / last, *hw_out = half its width (0: tgt cannot be drawn). Returns tgt, *lp = its log-prob. */
+static int planted_pick(const float* logits, int V1, int tgt, float* pbuf, double* cdf, float* lp_out,
+                        double* u_out, double* hw_out) {
+    float m, lse;
+    sample_cdf(logits, V1, pbuf, cdf, &m, &lse);
+    const double last = cdf[V1 - 1];
+    const double lo = tgt > 0 ? cdf[tgt - 1] : 0.0, hi = cdf[tgt];
+    *u_out = (lo + hi) / (2.0 * last);
+    *hw_out = (hi - lo) / (2.0 * last);
+    *lp_out = (logits[tgt] - m) - lse;
+    return tgt;
+}
+
+typedef struct {
+    const int32_t* targets;   /* [B*T] ids to aim the draws at */
+    double* u;                /* [B*T] out: the planted draws */
+    double* hw;               /* [B*T] out: half the width of each target's cdf interval */
+} od_plant;
+
 static int decode_core(const od_dims* d, const float* theta, const float* fc, int B, const double* u,
-                       int32_t* seq, float* lp, uint8_t* fragile, int half_order);
+                       const od_plant* plant, int32_t* seq, float* lp, uint8_t* fragile, int half_order);
 
 /*
  * Greedy decode of B unique rows with a (possibly perturbed) fp32 theta.
@@ -167,7 +195,7 @@ static int decode_core(const od_dims* d, const float* theta, const float* fc, in
  */
 int od_decode(const od_dims* d, const float* theta, const float* fc, int B,
               int32_t* seq, float* lp, uint8_t* fragile, int half_order) {
-    return decode_core(d, theta, fc, B, NULL, seq, lp, fragile, half_order);
+    return decode_core(d, theta, fc, B, NULL, NULL, seq, lp, fragile, half_order);
 }
 
 /*
@@ -178,11 +206,26 @@ int od_decode(const od_dims* d, const float* theta, const float* fc, int B,
  */
 int od_decode_sample(const od_dims* d, const float* theta, const float* fc, int B, const double* u,
                      int32_t* seq, float* lp, uint8_t* fragile, int half_order) {
-    return decode_core(d, theta, fc, B, u, seq, lp, fragile, half_order);
+    return decode_core(d, theta, fc, B, u, NULL, seq, lp, fragile, half_order);
+}
+
+/*
+ * od_decode_sample with the draws planted: at row b and logit step t the cdf is formed as sample_pick forms it and
+ * u[b*T + t-1] is set to the midpoint of targets[b*T + t-1]'s interval (hw: half the interval's width); the row goes
+ * on with that token (it = tok * unfinished as ever: a row that has drawn 0 stays ended and its draws go on). So
+ * od_decode_sample with these u returns seq, unless a half-width is within rounding of 0. fragile is not reported.
+ * No state outside the arguments: rows run under OpenMP.
+ */
+int od_decode_sample_planted(const od_dims* d, const float* theta, const float* fc, int B, const int32_t* targets,
+                             double* u, double* hw, int32_t* seq, float* lp, uint8_t* fragile, int half_order) {
+    const od_plant plant = {targets, u, hw};
+    for (size_t i = 0; i < (size_t)B * d->T; ++i)
+        if (targets[i] < 0 || targets[i] >= d->V1) return -1;
+    return decode_core(d, theta, fc, B, NULL, &plant, seq, lp, fragile, half_order);
 }
 
 static int decode_core(const od_dims* d, const float* theta, const float* fc, int B, const double* u,
-                       int32_t* seq, float* lp, uint8_t* fragile, int half_order) {
+                       const od_plant* plant, int32_t* seq, float* lp, uint8_t* fragile, int half_order) {
     const od_layout L = od_make_layout(d);
     const int E = d->E, R = d->R, F = d->F, V1 = d->V1, T = d->T, G = 5 * R;
     float* WimgT = transpose_perm(theta + L.img_w, E, F, half_order);
@@ -202,8 +245,9 @@ static int decode_core(const od_dims* d, const float* theta, const float* fc, in
         float* si = (float*)malloc(sizeof(float) * (size_t)G);
         float* sh = (float*)malloc(sizeof(float) * (size_t)G);
         float* logits = (float*)malloc(sizeof(float) * (size_t)V1);
-        float* pbuf = u ? (float*)malloc(sizeof(float) * (size_t)V1) : NULL;
-        double* cdf = u ? (double*)malloc(sizeof(double) * (size_t)V1) : NULL;
+        const int sampled = u != NULL || plant != NULL;
+        float* pbuf = sampled ? (float*)malloc(sizeof(float) * (size_t)V1) : NULL;
+        double* cdf = sampled ? (double*)malloc(sizeof(double) * (size_t)V1) : NULL;
         int unfinished = 1, it = 0;
         fin_step[b] = T;
         for (int t = 0; t <= T; ++t) {
@@ -224,9 +268,11 @@ static int decode_core(const od_dims* d, const float* theta, const float* fc, in
             if (t == 0) continue;                       /* t=0 logits are discarded */
             gemv_chain(WlT, theta + L.log_b, h, V1, R, half_order, logits);
             float lpv;
-            uint8_t fr;
-            int tok = u ? sample_pick(logits, V1, u[(size_t)b * T + t - 1], pbuf, cdf, &lpv, &fr)
-                        : greedy_pick(logits, V1, &lpv, &fr);
+            uint8_t fr = 0;
+            const size_t at = (size_t)b * T + t - 1;
+            int tok = plant ? planted_pick(logits, V1, plant->targets[at], pbuf, cdf, &lpv, &plant->u[at], &plant->hw[at])
+                      : u ? sample_pick(logits, V1, u[at], pbuf, cdf, &lpv, &fr)
+                          : greedy_pick(logits, V1, &lpv, &fr);
             if (tok > 0 && unfinished) unfinished = 1; else unfinished = 0;
             it = tok * unfinished;
             seq[(size_t)b * T + t - 1] = it;

@@ -10,6 +10,9 @@ Pieces and the reference lines they restate:
   perturb                    nets.py:113 (theta + delta, fp32) and
                              src/algorithm/nic_nes/nic_nes_worker.py:151 (theta - delta, fp32)
   decode                     oracle/nicnes_oracle.c (FCModel._sample, src/captioning/nets.py:183-245)
+  decode_sample_planted      decode_sample with each draw set to the midpoint of a chosen id's cdf interval
+                             (od_decode_sample_planted): aims the sampled pick at ids, for tests
+  sample_draws               the engine's counter-based draw stream (nicnes_sample_draws_kernel) in Python ints
   fitness                    CaptPolicy.rollout 'greedy', src/captioning/policies.py:125 via
                              oracle/cider_ref.py
   compute_ranks / centered   NESMaster.compute_ranks / compute_centered_ranks,
@@ -183,6 +186,45 @@ def decode_sample(dims, theta32, fc, u, half_order=0):
     lib().od_decode_sample(ctypes.byref(d), _p(theta32), _p(fc), ctypes.c_int(B), _p(u), _p(seq), _p(lp), _p(fr),
                            ctypes.c_int(half_order))
     return seq, lp, fr
+
+
+def decode_sample_planted(dims, theta32, fc, targets, half_order=0):
+    """decode_sample with the draws aimed: at row b and logit step t the cdf is formed as the sampled pick forms
+    it and u[b, t-1] is the midpoint of targets[b, t-1]'s interval, (cdf[tgt-1] + cdf[tgt]) / (2 last); the row
+    goes on with that token (a row that has drawn 0 stays ended, its draws go on). Returns (u f64 [B,T],
+    half_width f64 [B,T], seq int32 [B,T], lp f32 [B,T]); seq == targets wherever the row has not yet ended."""
+    theta32 = np.ascontiguousarray(theta32, np.float32)
+    fc = np.ascontiguousarray(fc, np.float32)
+    B = fc.shape[0]
+    targets = np.ascontiguousarray(targets, np.int32)
+    assert theta32.size == dims.D and fc.shape[1] == dims.F and targets.shape == (B, dims.T)
+    u = np.zeros((B, dims.T), np.float64)
+    hw = np.zeros((B, dims.T), np.float64)
+    seq = np.zeros((B, dims.T), np.int32)
+    lp = np.zeros((B, dims.T), np.float32)
+    fr = np.zeros((B, dims.T), np.uint8)
+    d = dims.c()
+    rc = lib().od_decode_sample_planted(ctypes.byref(d), _p(theta32), _p(fc), ctypes.c_int(B), _p(targets), _p(u),
+                                        _p(hw), _p(seq), _p(lp), _p(fr), ctypes.c_int(half_order))
+    if rc < 0:
+        raise ValueError('decode_sample_planted: a target outside [0, V1)')
+    return u, hw, seq, lp
+
+
+SAMPLE_DRAWS_SALT = 0x6a09e667f3bcc909
+
+
+def sample_draws(seed, iteration, member0, count, B, T):
+    """The engine's own uniforms of a sampled decode (nicnes_sample_draws_kernel, update_kernels.hip), restated
+    with Python ints: [count, 2, B, T] fp64, member member0 + k's stream keyed by
+    splitmix64(seed ^ salt ^ ((iteration << 32) | (member0 + k))), u = (splitmix64(key ^ r) >> 11) * 2^-53 with
+    r the flat index in [2, B, T]."""
+    out = np.empty((count, 2 * B * T), np.float64)
+    for k in range(count):
+        key = splitmix64((seed ^ SAMPLE_DRAWS_SALT ^ (((iteration << 32) | (member0 + k)) & MASK64)) & MASK64)
+        for r in range(2 * B * T):
+            out[k, r] = (splitmix64(key ^ r) >> 11) * (1.0 / 9007199254740992.0)
+    return out.reshape(count, 2, B, T)
 
 
 def gemv(W, bias, x, half_order=0):

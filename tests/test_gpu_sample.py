@@ -50,13 +50,15 @@ def _load(eng, theta, fc, seed=11, n_refs=5):
 _COVERAGE = {}
 
 
-def _write_coverage():
+def _write_coverage(name='sample_reference_coverage.json', data=None):
+    """data (default: this module's coverage record) as JSON into the run's output directory; also used by
+    tests/test_gpu_sample_pick.py for its own reports."""
     import json
     import os
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
     os.makedirs(out, exist_ok=True)
-    with open(os.path.join(out, 'sample_reference_coverage.json'), 'w') as f:
-        json.dump(_COVERAGE, f, indent=1)
+    with open(os.path.join(out, name), 'w') as f:
+        json.dump(_COVERAGE if data is None else data, f, indent=1, sort_keys=data is not None)
 
 
 def _rows_agree(got, want, stop):
