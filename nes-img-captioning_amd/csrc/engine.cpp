@@ -1231,16 +1231,128 @@ static int score_rollouts(nicnes_handle* h, const int32_t* seq, const float* lp,
     return NICNES_OK;
 }
 
-// The decode of `count` members enqueued on s, or in parts on s and the engine's streams (the one launch sequence of
-// nicnes_evaluate* and nicnes_split_decode). Returns the number of streams used, or -(error code).
-static int launch_decode_parts(nicnes_handle* h, const DecodeParams& p, const MutHead& mh, const ScreenArgs& sa, int count,
-                               int nslabs, hipStream_t s, bool timed, int* n_ev, const QueueArgs* qa = nullptr) {
+// ---- a decode request, piece by piece: what every site that builds a DecodeParams shares -------------------------
+// What the handle alone fixes; everything else is zero. Each site adds its buffers, its shape (B, B_img, rpi, sign_off,
+// G, S, coop) and its switches (no_exit, test_stall_ms) itself.
+static DecodeParams decode_base(const nicnes_handle* h) {
+    DecodeParams p{};
+    p.F = h->cfg.fc_feat_size;
+    p.V1 = h->V1;
+    p.T = h->cfg.seq_length;
+    p.D = h->D;
+    p.off_img_w = h->off[0];
+    p.off_img_b = h->off[1];
+    p.off_emb_w = h->off[2];
+    p.off_log_w = h->off[3];
+    p.off_log_b = h->off[4];
+    p.off_i2h_w = h->off[5];
+    p.off_i2h_b = h->off[6];
+    p.off_h2h_w = h->off[7];
+    p.off_h2h_b = h->off[8];
+    p.stats = h->stats;
+    p.force_exact = h->force_exact;
+    p.lse_margin = h->lse_margin;
+    p.coop_launch = h->coop_launch;
+    return p;
+}
+
+// h->noise_sc = fp32(sigma * z), the table scaled once per sigma (its bit pattern): the plain decode's noise, and the
+// sigma z a mutated fused decode forms the head parameters' delta' from. Allocated at the first use.
+static int ensure_noise_scaled(nicnes_handle* h, float sigma, hipStream_t s) {
+    if (!h->noise_sc) {
+        HIPC(h, hipDeviceSynchronize());
+        int rc = dalloc(h, &h->noise_sc, (size_t)h->cfg.noise_len);
+        if (rc) return rc;
+    }
+    if (!h->sc_valid || __builtin_bit_cast(uint32_t, h->sc_sigma) != __builtin_bit_cast(uint32_t, sigma)) {
+        HIPC(h, nicnes_launch_scale(h->noise, h->noise_sc, h->cfg.noise_len, sigma, s));
+        h->sc_sigma = sigma;
+        h->sc_valid = true;
+    }
+    return NICNES_OK;
+}
+
+// The members' mutated delta' rows [max_members, Dp] and their row offsets k * Dp, allocated at the first mutated
+// decode (the handle's safe / proportional mutations, nic_es's proportional one)
+static int ensure_delta_rows(nicnes_handle* h, float** dbuf, uint64_t** didx, int64_t Dp, hipStream_t s) {
+    if (*dbuf) return NICNES_OK;
+    HIPC(h, hipDeviceSynchronize());
+    int rc = dalloc(h, dbuf, (size_t)h->cfg.max_members * (size_t)Dp);
+    if (!rc) rc = dalloc(h, didx, (size_t)h->cfg.max_members);
+    if (rc) return rc;
+    HIPC(h, nicnes_launch_iota_stride(*didx, h->cfg.max_members, (uint64_t)Dp, s));
+    return NICNES_OK;
+}
+
+// The bounded-lse policy (nicnes_handle::bounded_mode) and the read-back of the decode counters that drives it, in the
+// order an evaluate calls them. lse_poll: a finished read-back's faults reported, and two or more new fallbacks of a
+// bounded decode send the next 32 decodes to the exact sum.
+static int lse_poll(nicnes_handle* h) {
+    if (!h->stats_pending || hipEventQuery(h->stats_ev) != hipSuccess) return NICNES_OK;
+    const int32_t fb = h->stats_host[0];
+    if (h->stats_host[2] != 0)
+        return fail(h, NICNES_ERR_FAULT, "coop decode: a workgroup's partners never arrived (hand-off timeout)");
+    if (h->stats_host[3] != 0)
+        return fail(h, NICNES_ERR_FAULT, "sampled decode: a workgroup found no free logit slot");
+    if (h->last_bounded && fb - h->fb_seen >= 2) h->exact_left = 32;
+    h->fb_seen = fb;
+    h->stats_pending = false;
+    return NICNES_OK;
+}
+
+// the policy as it stands (nicnes_split_decode reads it without advancing it: tokens do not depend on the lse mode)
+static bool lse_bounded_now(const nicnes_handle* h) {
+    return h->bounded_mode == 1 || (h->bounded_mode == 2 && h->exact_left == 0);
+}
+
+// the lse mode of the decode being built; a greedy-only one (no log-probs) spends one of the exact decodes left
+static bool lse_decide(nicnes_handle* h, bool greedy_only) {
+    const bool bounded = lse_bounded_now(h);
+    if (h->bounded_mode == 2 && h->exact_left > 0 && greedy_only) --h->exact_left;
+    h->last_decode_bounded = (bounded && greedy_only) ? 1 : 0;
+    return bounded;
+}
+
+// after the launch: the counters read back without a host wait, unless a read-back is still in flight
+static int lse_arm(nicnes_handle* h, bool bounded_greedy, hipStream_t s) {
+    if (h->stats_pending) return NICNES_OK;
+    HIPC(h, hipMemcpyAsync(h->stats_host, h->stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(h, hipEventRecord(h->stats_ev, s));
+    h->stats_pending = true;
+    h->last_bounded = bounded_greedy;
+    return NICNES_OK;
+}
+
+// The screened logit loop's arguments for a decode of `members` members in `workgroups` fused workgroups: its buffers
+// when the caller's path allows it (eligible), the mode asks for it and the decode fits them, else cap == NULL (the
+// fp32 loop). Automatic mode: from one workgroup per CU on (P = 256, B = 128: 15.7 ms an iteration screened against
+// 23.05 ms unscreened); fewer workgroups than CUs were not measured. The buffers (ensure_screen, at create
+// or at the setter: nothing is allocated here) hold screen_wgs capture slots and max_members rows of norms.
+static ScreenArgs pick_screen(const nicnes_handle* h, int members, int64_t workgroups, bool eligible) {
+    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr, h->screen_rounds};
+    const bool on = h->screen_mode == 1 || (h->screen_mode == 2 && workgroups >= h->n_cu);
+    if (eligible && on && h->screen_cap && h->screen_norm && workgroups <= h->screen_wgs &&
+        members <= h->cfg.max_members) {
+        sa.cap = h->screen_cap;
+        sa.norm = h->screen_norm;
+    }
+    return sa;
+}
+
+// The decode of `count` members enqueued on s, or in parts on s and the engine's streams: the one fork/join of
+// nicnes_evaluate*, nicnes_split_decode and nicnes_es_evaluate. With pa (nic_es: members with their own base theta)
+// the launches are nicnes_launch_decode_es, which takes no MutHead, timing events or queue. Returns the number of
+// streams used, or -(error code).
+static int launch_decode_parts(nicnes_handle* h, const DecodeParams& p, const MutHead& mh, const ScreenArgs& sa,
+                               const QueueArgs* qa, const ParentArgs* pa, int count, int nslabs, hipStream_t s, bool timed,
+                               int* n_ev) {
 #define HIPN(expr)                                                                                           \
     do {                                                                                                     \
         hipError_t e_ = (expr);                                                                              \
         if (e_ != hipSuccess) return -fail(h, NICNES_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
-    // the coop launch needs all its workgroups resident: never split over streams
+    // the coop launch needs all its workgroups resident: never split over streams. (nic_es decodes with S == 1 unless
+    // coop, so the same rule gives it one stream unless nicnes_set_decode_streams asks for more)
     const int nstr = p.coop ? 1 : std::min(count, h->dec_streams ? h->dec_streams : (p.S == 1 ? 1 : 2));
     if (nstr > 1) {
         // members split evenly over the caller's stream and nstr - 1 engine streams; the parts share
@@ -1257,21 +1369,54 @@ static int launch_decode_parts(nicnes_handle* h, const DecodeParams& p, const Mu
             DecodeParams pi = p;
             MutHead mi = mh;
             ScreenArgs si_ = sa;
-            nicnes_decode_shift(&pi, a, nslabs, &mi, &si_);
+            ParentArgs pa_i = pa ? *pa : ParentArgs{};
+            nicnes_decode_shift(&pi, a, nslabs, pa ? nullptr : &mi, &si_, pa ? &pa_i : nullptr);
             hipStream_t si = i == 0 ? s : h->sx[i - 1];
             if (i > 0) HIPN(hipStreamWaitEvent(si, h->ev_fork, 0));
-            HIPN(nicnes_launch_decode(&pi, &mi, b - a, nslabs, si, nullptr, nullptr, nullptr, &si_));
+            if (pa)
+                HIPN(nicnes_launch_decode_es(&pi, &pa_i, b - a, nslabs, si, &si_));
+            else
+                HIPN(nicnes_launch_decode(&pi, &mi, b - a, nslabs, si, nullptr, nullptr, nullptr, &si_));
         }
         for (int i = 0; i < nstr - 1; ++i) {
             HIPN(hipEventRecord(h->ev_join[i], h->sx[i]));
             HIPN(hipStreamWaitEvent(s, h->ev_join[i], 0));
         }
+    } else if (pa) {
+        HIPN(nicnes_launch_decode_es(&p, pa, count, nslabs, s, &sa));
     } else {
         // (the step queue: only a decode in one part; the parts of a decode over several streams would share its ring)
         HIPN(nicnes_launch_decode(&p, &mh, count, nslabs, s, timed ? h->dev : nullptr, h->dev_kind, n_ev, &sa, qa));
     }
 #undef HIPN
     return nstr;
+}
+
+// The tail both evaluates share, from the zeroed outputs to the last timing event: the decode of `count` members
+// into p.seq / p.lp (out_rows rows), the log-prob exit pass, the counter read-back and the scoring of the n_cand
+// rollouts of rows_total rows each (n_cand is also the lp pass's rollout count: 2 * count, or eval_theta's 1).
+static int decode_and_score(nicnes_handle* h, const DecodeParams& p, const MutHead& mh, const ScreenArgs& sa,
+                            const QueueArgs* qa, const ParentArgs* pa, int count, int nslabs, size_t out_rows, int n_cand,
+                            int rows_total, int rpi, const int32_t* mb, const double* base, double* fitness_out,
+                            double* scores_out, hipStream_t s) {
+    // rows a member never writes (all finished early) must read as 0 (nets.py:188 zeros)
+    HIPC(h, hipMemsetAsync(p.seq, 0, out_rows * h->cfg.seq_length * sizeof(int32_t), s));
+    if (p.lp) HIPC(h, hipMemsetAsync(p.lp, 0, out_rows * h->cfg.seq_length * sizeof(float), s));
+    if (h->timing) HIPC(h, hipEventRecord(h->ev[0], s));
+    int n_ev = 0;
+    const int nstr = launch_decode_parts(h, p, mh, sa, qa, pa, count, nslabs, s, h->timing, &n_ev);
+    if (nstr < 0) return -nstr;
+    h->n_dev = h->timing ? n_ev : 0;      // (nic_es launches record no events: 0)
+    h->multi_stream = nstr > 1;
+    // log-probs of a no_exit decode past the batch's last finishing step. Also with one slab: its workgroup holds both
+    // signs and runs until the later of the two has finished, writing the earlier one's log-probs past that rollout's own
+    // last step (eval_theta: the two halves are one rollout)
+    if (p.lp) HIPC(h, nicnes_launch_lp_batch_exit(p.seq, p.lp, n_cand, rows_total, h->cfg.seq_length, s));
+    if (h->timing) HIPC(h, hipEventRecord(h->ev[1], s));
+    if (int rc = lse_arm(h, p.bounded_lse && !p.lp, s)) return rc;
+    if (int rc = score_rollouts(h, p.seq, p.lp, n_cand, rows_total, rpi, mb, base, fitness_out, scores_out, s)) return rc;
+    if (h->timing) HIPC(h, hipEventRecord(h->ev[2], s));
+    return NICNES_OK;
 }
 
 // eval_theta: the sigma = 0 rollout of theta itself (count 1), decoded ONCE: sign + takes the first half of the
@@ -1317,10 +1462,8 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     if (int rc = ensure_rows(h, rows_total)) return rc;
     const int32_t* mb = nullptr;
     if (int rc = stage_member_batch(h, member_batch_host, count, s, &mb)) return rc;
-    DecodeParams p;
+    DecodeParams p = decode_base(h);
     p.theta = h->theta32;
-    p.noise = h->noise;
-    p.noise_idx = h->nidx;
     if (eval_theta) {       // theta itself: a zero slice (the sigma-scaled table is left as it is)
         int rc = ensure_zero_noise(h);
         if (rc) return rc;
@@ -1329,34 +1472,15 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     } else {
         HIPC(h, nicnes_launch_noise_index(h->cfg.noise_seed, iteration, (uint64_t)member_begin, count, h->cfg.noise_len,
                                           (uint64_t)h->D, h->nidx, s));
-    }
-    if (eval_theta) {
-    } else if (h->mut_mode && !h->dbuf) {   // first mutated evaluation: [max_members, Dp] delta' rows
-        HIPC(h, hipDeviceSynchronize());
-        h->Dp = (h->D + 63) / 64 * 64;
-        int rc = dalloc(h, &h->dbuf, (size_t)h->cfg.max_members * (size_t)h->Dp);
-        if (!rc) rc = dalloc(h, &h->didx, (size_t)h->cfg.max_members);
-        if (rc) return rc;
-        HIPC(h, nicnes_launch_iota_stride(h->didx, h->cfg.max_members, (uint64_t)h->Dp, s));
-    }
-    if (!eval_theta) {      // fp32(sigma * z), the table scaled once per sigma: the plain decode's noise, and the
-        if (!h->noise_sc) { // sigma z a mutated fused decode forms the head parameters' delta' from (below)
-            HIPC(h, hipDeviceSynchronize());
-            int rc = dalloc(h, &h->noise_sc, (size_t)h->cfg.noise_len);
-            if (rc) return rc;
+        if (h->mut_mode) {
+            h->Dp = (h->D + 63) / 64 * 64;
+            if (int rc = ensure_delta_rows(h, &h->dbuf, &h->didx, h->Dp, s)) return rc;
         }
-        if (!h->sc_valid || __builtin_bit_cast(uint32_t, h->sc_sigma) != __builtin_bit_cast(uint32_t, sigma)) {
-            HIPC(h, nicnes_launch_scale(h->noise, h->noise_sc, h->cfg.noise_len, sigma, s));
-            h->sc_sigma = sigma;
-            h->sc_valid = true;
-        }
-    }
-    if (eval_theta) {
-    } else if (h->mut_mode) {      // safe / proportional mutations: the decode reads the members' delta' rows
-        p.noise = h->dbuf;         // (materialised below, once the decode path is known)
-        p.noise_idx = h->didx;
-    } else {
-        p.noise = h->noise_sc;
+        if (int rc = ensure_noise_scaled(h, sigma, s)) return rc;
+        // safe / proportional mutations: the decode reads the members' delta' rows (materialised below, once the
+        // decode path is known)
+        p.noise = h->mut_mode ? h->dbuf : h->noise_sc;
+        p.noise_idx = h->mut_mode ? h->didx : h->nidx;
     }
     MutHead mh{nullptr, nullptr, nullptr, 0};
     p.fc = h->fc;
@@ -1365,29 +1489,11 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     const bool crit_lp = (mode >= NICNES_FITNESS_GREEDY_LOGPROB && mode <= NICNES_FITNESS_GREEDY_AVGPROB) ||
                          mode == NICNES_FITNESS_SC_LOSS;                // the criterion needs seq_logprobs
     p.lp = logprob_out ? logprob_out : (crit_lp ? h->lp : nullptr);
-    p.sample_u = nullptr;
-    p.slog = nullptr;
-    p.slog_slots = nullptr;
-    p.slog_ns = 0;
     p.scratch = h->dscratch;
-    p.stats = h->stats;
     p.alive = h->alive;
-    p.force_exact = h->force_exact;
-    p.lse_margin = h->lse_margin;
-    if (h->stats_pending && hipEventQuery(h->stats_ev) == hipSuccess) {   // the last decode's fallbacks
-        const int32_t fb = h->stats_host[0];
-        if (h->stats_host[2] != 0)
-            return fail(h, NICNES_ERR_FAULT, "coop decode: a workgroup's partners never arrived (hand-off timeout)");
-        if (h->stats_host[3] != 0)
-            return fail(h, NICNES_ERR_FAULT, "sampled decode: a workgroup found no free logit slot");
-        if (h->last_bounded && fb - h->fb_seen >= 2) h->exact_left = 32;
-        h->fb_seen = fb;
-        h->stats_pending = false;
-    }
-    bool bounded = h->bounded_mode == 1 || (h->bounded_mode == 2 && h->exact_left == 0);
-    if (h->bounded_mode == 2 && h->exact_left > 0 && !p.lp) --h->exact_left;
+    if (int rc = lse_poll(h)) return rc;          // the last decode's fallbacks
+    const bool bounded = lse_decide(h, !p.lp);
     p.bounded_lse = bounded ? 1 : 0;
-    h->last_decode_bounded = (bounded && !p.lp) ? 1 : 0;
     // rows per sign: all of the rollout's rows, or the first half (eval_theta; sign - takes rows half + b)
     const int rows = eval_theta ? (rows_total + 1) / 2 : rows_total;
     int G = 0, nslabs = 0, S = 0;
@@ -1437,19 +1543,8 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     }
     if ((int64_t)count * nslabs * S > h->part_cap)
         return fail(h, NICNES_ERR_INVALID, "decode split beyond the partial-state buffer (nicnes_set_decode_split)");
-    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr, h->screen_rounds};
-    // automatic: from one workgroup per CU on (P = 256, B = 128: 15.7 ms an iteration screened against 23.05 ms
-    // unscreened; with the certify spread over the workgroup a launch of one round of workgroups no longer
-    // waits on a slow one). Fewer workgroups than CUs: not measured, the fp32 loop as before
-    const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)count * nslabs >= h->n_cu);
-    if (screen_on && !sampled && !p.lp && bounded && G == 4 && S == 1 && !(h->mut_mode && !eval_theta)) {
-        // the screened logit loop: a capture slot per workgroup and the members' norms (ensure_screen, at create or
-        // at the setter: nothing is allocated here); a decode of more workgroups than slots runs the fp32 loop
-        if (h->screen_cap && h->screen_norm && (int64_t)count * nslabs <= h->screen_wgs) {
-            sa.cap = h->screen_cap;
-            sa.norm = h->screen_norm;
-        }
-    }
+    const ScreenArgs sa = pick_screen(h, count, (int64_t)count * nslabs,
+                                      !sampled && !p.lp && bounded && G == 4 && S == 1 && !(h->mut_mode && !eval_theta));
     // the screened decode from the step queue: more member slabs than workers (automatic), or forced on
     QueueArgs qa{nullptr, nullptr, 0, 0};
     {
@@ -1462,7 +1557,6 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     p.S = S;
     p.part = h->part;
     p.coop = !sampled && coop_fits(h, G, nslabs, S, count) ? 1 : 0;
-    p.coop_launch = h->coop_launch;
     if (!eval_theta && h->mut_mode) {
         // the members' delta' rows. On the fused greedy path only the parameters from off_log_w on (logit, i2h, h2h,
         // which every step re-reads) are materialised; the decode forms the image projection's and the embedding
@@ -1478,7 +1572,6 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     // log-probs of a batch spread over several slabs: every slab runs to T, then the steps after the
     // batch's last finishing step are zeroed (nicnes_lp_batch_exit), as FCModel._sample leaves them
     p.no_exit = (p.lp && nslabs > 1) ? 1 : 0;
-    p.no_mask = 0;
     p.coop_ctr = h->coop_ctr;
     p.alive2 = h->alive + h->alive_stride;
     p.alive_stride = h->alive_stride;
@@ -1486,46 +1579,12 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     p.B_img = h->B;
     p.rpi = rpi;
     p.sign_off = eval_theta ? rows : 0;
-    p.F = h->cfg.fc_feat_size;
-    p.V1 = h->V1;
-    p.T = h->cfg.seq_length;
-    p.D = h->D;
-    p.off_img_w = h->off[0];
-    p.off_img_b = h->off[1];
-    p.off_emb_w = h->off[2];
-    p.off_log_w = h->off[3];
-    p.off_log_b = h->off[4];
-    p.off_i2h_w = h->off[5];
-    p.off_i2h_b = h->off[6];
-    p.off_h2h_w = h->off[7];
-    p.off_h2h_b = h->off[8];
-    // rows a member never writes (all finished early) must read as 0 (nets.py:188 zeros). eval_theta's output is
-    // the one rollout of rows_total rows (with an odd count sign - has one row fewer than sign +)
+    // eval_theta's output is the one rollout of rows_total rows (with an odd count sign - has one row fewer than
+    // sign +), rows s * half + b = image s * half + b
     const size_t out_rows = eval_theta ? (size_t)rows_total : (size_t)count * 2 * rows;
-    HIPC(h, hipMemsetAsync(p.seq, 0, out_rows * h->cfg.seq_length * sizeof(int32_t), s));
-    if (p.lp) HIPC(h, hipMemsetAsync(p.lp, 0, out_rows * h->cfg.seq_length * sizeof(float), s));
-    if (h->timing) HIPC(h, hipEventRecord(h->ev[0], s));
-    int n_ev = 0;
-    const int nstr = launch_decode_parts(h, p, mh, sa, count, nslabs, s, h->timing, &n_ev, &qa);
-    if (nstr < 0) return -nstr;
-    h->n_dev = h->timing ? n_ev : 0;
-    h->multi_stream = nstr > 1;
-    // also with one slab: its workgroup holds both signs and runs until the later of the two has finished, writing the
-    // earlier one's log-probs past that rollout's own last step (eval_theta: the two halves are one rollout)
-    if (p.lp)
-        HIPC(h, nicnes_launch_lp_batch_exit(p.seq, p.lp, eval_theta ? 1 : 2 * count, rows_total, h->cfg.seq_length, s));
-    if (h->timing) HIPC(h, hipEventRecord(h->ev[1], s));
-    if (!h->stats_pending) {          // read the fallback counter back without a host wait
-        HIPC(h, hipMemcpyAsync(h->stats_host, h->stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIPC(h, hipEventRecord(h->stats_ev, s));
-        h->stats_pending = true;
-        h->last_bounded = bounded && !p.lp;
-    }
-    const int n_cand = eval_theta ? 1 : 2 * count;      // eval_theta: rows s * half + b = image s * half + b
-    const double* base = self_critical ? h->base_scores : nullptr;
-    if (int rc = score_rollouts(h, p.seq, p.lp, n_cand, rows_total, rpi, mb, base, fitness_out, scores_out, s)) return rc;
-    if (h->timing) HIPC(h, hipEventRecord(h->ev[2], s));
-    return NICNES_OK;
+    const int n_cand = eval_theta ? 1 : 2 * count;
+    return decode_and_score(h, p, mh, sa, &qa, nullptr, count, nslabs, out_rows, n_cand, rows_total, rpi, mb,
+                            self_critical ? h->base_scores : nullptr, fitness_out, scores_out, s);
 }
 
 int nicnes_evaluate_batches(nicnes_handle* h, uint64_t iteration, int32_t member_begin, int32_t count, float sigma,
@@ -1735,7 +1794,7 @@ static int split_decode_impl(nicnes_handle* h, nicnes_split* sp, int32_t first, 
     if (int rc = ensure_zero_noise(h)) return rc;
     if (int rc = split_grow(h, sp, n_pm, (int64_t)n_pm * nslabs * S)) return rc;
     const int T = h->cfg.seq_length;
-    DecodeParams p;
+    DecodeParams p = decode_base(h);
     p.theta = h->theta32;
     p.noise = h->zero_noise;
     p.noise_idx = sp->zero_idx;
@@ -1743,59 +1802,30 @@ static int split_decode_impl(nicnes_handle* h, nicnes_split* sp, int32_t first, 
     p.member_batch = sp->block;
     p.seq = sp->seq;
     p.lp = lp_out ? sp->lp : nullptr;
-    p.sample_u = nullptr;
-    p.slog = nullptr;
-    p.slog_slots = nullptr;
-    p.slog_ns = 0;
     p.scratch = sp->scratch;
-    p.stats = h->stats;
     p.alive = sp->alive;
     p.alive_stride = 2 * sp->pm_cap;
     p.alive2 = sp->alive + p.alive_stride;
     p.part = sp->part;
     p.coop_ctr = sp->coop_ctr;
-    p.force_exact = h->force_exact;
-    p.lse_margin = h->lse_margin;
-    // the lse mode of the engine's policy as it stands (tokens do not depend on it); the policy's own state and the
-    // counter read-back belong to the evaluates
-    const bool bounded = h->bounded_mode == 1 || (h->bounded_mode == 2 && h->exact_left == 0);
+    // the lse mode of the engine's policy as it stands; the policy's own state and the counter read-back belong to the
+    // evaluates
+    const bool bounded = lse_bounded_now(h);
     p.bounded_lse = bounded ? 1 : 0;
-    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr, h->screen_rounds};
-    const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)n_pm * nslabs >= h->n_cu);
-    if (screen_on && !p.lp && bounded && G == 4 && S == 1 && h->screen_cap && h->screen_norm &&
-        (int64_t)n_pm * nslabs <= h->screen_wgs && n_pm <= h->cfg.max_members) {
-        sa.cap = h->screen_cap;
-        sa.norm = h->screen_norm;
-    }
+    const ScreenArgs sa = pick_screen(h, n_pm, (int64_t)n_pm * nslabs, !p.lp && bounded && G == 4 && S == 1);
     p.G = G;
     p.S = S;
     p.coop = coop_fits(h, G, nslabs, S, n_pm) ? 1 : 0;
-    p.coop_launch = h->coop_launch;
-    p.test_stall_ms = 0;
-    p.no_exit = 0;      // a row's log-probs up to its own end token are written before its workgroup exits
-    p.no_mask = 0;
+    // (no_exit stays 0: a row's log-probs up to its own end token are written before its workgroup exits)
     p.B = SPLIT_ROWS;
     p.B_img = per;
     p.rpi = 1;
     p.sign_off = SPLIT_ROWS;
-    p.F = h->cfg.fc_feat_size;
-    p.V1 = h->V1;
-    p.T = T;
-    p.D = h->D;
-    p.off_img_w = h->off[0];
-    p.off_img_b = h->off[1];
-    p.off_emb_w = h->off[2];
-    p.off_log_w = h->off[3];
-    p.off_log_b = h->off[4];
-    p.off_i2h_w = h->off[5];
-    p.off_i2h_b = h->off[6];
-    p.off_h2h_w = h->off[7];
-    p.off_h2h_b = h->off[8];
     const size_t out_rows = (size_t)n_pm * per;
     HIPC(h, hipMemsetAsync(p.seq, 0, out_rows * T * sizeof(int32_t), s));
     if (p.lp) HIPC(h, hipMemsetAsync(p.lp, 0, out_rows * T * sizeof(float), s));
     const MutHead mh{nullptr, nullptr, nullptr, 0};
-    const int nstr = launch_decode_parts(h, p, mh, sa, n_pm, nslabs, s, false, nullptr);
+    const int nstr = launch_decode_parts(h, p, mh, sa, nullptr, nullptr, n_pm, nslabs, s, false, nullptr);
     if (nstr < 0) return -nstr;
     if (p.lp) {
         hipLaunchKernelGGL(split_lp_mask_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s,
@@ -2223,23 +2253,10 @@ int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member
     if (h->mut_mode) return fail(h, NICNES_ERR_UNSUPPORTED, "nicnes_test_logit_chain: plain mutations only");
     hipStream_t s = (hipStream_t)stream;
     HIPC(h, hipSetDevice(h->device));
-    if (!h->noise_sc) {
-        HIPC(h, hipDeviceSynchronize());
-        int rc = dalloc(h, &h->noise_sc, (size_t)h->cfg.noise_len);
-        if (rc) return rc;
-    }
-    if (!h->sc_valid || __builtin_bit_cast(uint32_t, h->sc_sigma) != __builtin_bit_cast(uint32_t, sigma)) {
-        HIPC(h, nicnes_launch_scale(h->noise, h->noise_sc, h->cfg.noise_len, sigma, s));
-        h->sc_sigma = sigma;
-        h->sc_valid = true;
-    }
-    DecodeParams p{};
+    if (int rc = ensure_noise_scaled(h, sigma, s)) return rc;
+    DecodeParams p = decode_base(h);
     p.theta = h->theta32;
     p.noise = h->noise_sc;
-    p.V1 = h->V1;
-    p.D = h->D;
-    p.off_log_w = h->off[3];
-    p.off_log_b = h->off[4];
     p.scratch = h->dscratch;        // one wave's lane scratch holds the rows of h (no decode runs beside this)
     const uint64_t nidx = nn_noise_index(h->cfg.noise_seed, iteration, (uint64_t)member, h->cfg.noise_len, (uint64_t)h->D);
     HIPC(h, nicnes_launch_test_logit_chain(&p, nidx, sign, h_rows, out_mfma, out_chain, s));
@@ -2267,16 +2284,7 @@ int nicnes_test_certify_items_owned(nicnes_handle* h, uint64_t iteration, int32_
     }
     hipStream_t s = (hipStream_t)stream;
     HIPC(h, hipSetDevice(h->device));
-    if (!h->noise_sc) {
-        HIPC(h, hipDeviceSynchronize());
-        int rc = dalloc(h, &h->noise_sc, (size_t)h->cfg.noise_len);
-        if (rc) return rc;
-    }
-    if (!h->sc_valid || __builtin_bit_cast(uint32_t, h->sc_sigma) != __builtin_bit_cast(uint32_t, sigma)) {
-        HIPC(h, nicnes_launch_scale(h->noise, h->noise_sc, h->cfg.noise_len, sigma, s));
-        h->sc_sigma = sigma;
-        h->sc_valid = true;
-    }
+    if (int rc = ensure_noise_scaled(h, sigma, s)) return rc;
     // the items grouped by owner lane (group 2 row + half; half 0, or the id's bit 2 as the decode's lists have it):
     // lane_start [257] | ids [n] | positions [n]. Inside a group the caller's order, or increasing ids (by id: the order
     // a decode's lane meets them in; repeats keep the caller's order)
@@ -2301,13 +2309,9 @@ int nicnes_test_certify_items_owned(nicnes_handle* h, uint64_t iteration, int32_
     int32_t* dev = nullptr;
     HIPC(h, hipMalloc((void**)&dev, host.size() * sizeof(int32_t)));
     hipError_t e = hipMemcpyAsync(dev, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    DecodeParams p{};
+    DecodeParams p = decode_base(h);
     p.theta = h->theta32;
     p.noise = h->noise_sc;
-    p.V1 = h->V1;
-    p.D = h->D;
-    p.off_log_w = h->off[3];
-    p.off_log_b = h->off[4];
     p.scratch = h->dscratch;        // eight waves' lane scratch hold the rows of h (no decode runs beside this)
     const uint64_t nidx = nn_noise_index(h->cfg.noise_seed, iteration, (uint64_t)member, h->cfg.noise_len, (uint64_t)h->D);
     if (e == hipSuccess)
@@ -2833,31 +2837,16 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
     if (int rc = es_stage_i32(h, parent_of_host, count, es->n_parents, es->parent_of, s, "parent_of")) return rc;
     HIPC(h, nicnes_launch_noise_index(h->cfg.noise_seed, generation, (uint64_t)pair_begin, count, h->cfg.noise_len,
                                       (uint64_t)h->D, h->nidx, s));
-    DecodeParams p{};
+    DecodeParams p = decode_base(h);
     p.theta = es->ptab[es->cur];       // (every *_es kernel sets its workgroup's base from ParentArgs)
-    if (es->mode) {
-        if (!es->dbuf) {               // first proportional evaluate: [max_members, Dp] delta' rows, as dbuf
-            HIPC(h, hipDeviceSynchronize());
-            int rc = dalloc(h, &es->dbuf, (size_t)h->cfg.max_members * (size_t)es->Dp);
-            if (!rc) rc = dalloc(h, &es->didx, (size_t)h->cfg.max_members);
-            if (rc) return rc;
-            HIPC(h, nicnes_launch_iota_stride(es->didx, h->cfg.max_members, (uint64_t)es->Dp, s));
-        }
+    if (es->mode) {                    // proportional: the pairs' delta' rows
+        if (int rc = ensure_delta_rows(h, &es->dbuf, &es->didx, es->Dp, s)) return rc;
         HIPC(h, nicnes_launch_es_mutate(h->noise, h->nidx, count, es->ptab[es->cur], es->parent_of, es->pmean[es->cur],
                                         es->Dp, h->D, sigma, es->dbuf, s));
         p.noise = es->dbuf;
         p.noise_idx = es->didx;
-    } else {                           // plain: the sigma-scaled table, as nicnes_evaluate
-        if (!h->noise_sc) {
-            HIPC(h, hipDeviceSynchronize());
-            int rc = dalloc(h, &h->noise_sc, (size_t)h->cfg.noise_len);
-            if (rc) return rc;
-        }
-        if (!h->sc_valid || __builtin_bit_cast(uint32_t, h->sc_sigma) != __builtin_bit_cast(uint32_t, sigma)) {
-            HIPC(h, nicnes_launch_scale(h->noise, h->noise_sc, h->cfg.noise_len, sigma, s));
-            h->sc_sigma = sigma;
-            h->sc_valid = true;
-        }
+    } else {                           // plain: the sigma-scaled table
+        if (int rc = ensure_noise_scaled(h, sigma, s)) return rc;
         p.noise = h->noise_sc;
         p.noise_idx = h->nidx;
     }
@@ -2867,36 +2856,17 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
     const bool crit_lp = mode >= NICNES_FITNESS_GREEDY_LOGPROB && mode <= NICNES_FITNESS_GREEDY_AVGPROB;
     p.lp = logprob_out ? logprob_out : (crit_lp ? h->lp : nullptr);
     p.scratch = h->dscratch;
-    p.stats = h->stats;
     p.alive = h->alive;
-    p.force_exact = h->force_exact;
-    p.lse_margin = h->lse_margin;
-    // the bounded-lse policy and the fault read-back of evaluate_impl
-    if (h->stats_pending && hipEventQuery(h->stats_ev) == hipSuccess) {
-        const int32_t fb = h->stats_host[0];
-        if (h->stats_host[2] != 0 || h->stats_host[3] != 0)
-            return fail(h, NICNES_ERR_FAULT, "a decode on this handle lost rows (nicnes_stats, nicnes_clear_faults)");
-        if (h->last_bounded && fb - h->fb_seen >= 2) h->exact_left = 32;
-        h->fb_seen = fb;
-        h->stats_pending = false;
-    }
-    const bool bounded = h->bounded_mode == 1 || (h->bounded_mode == 2 && h->exact_left == 0);
-    if (h->bounded_mode == 2 && h->exact_left > 0 && !p.lp) --h->exact_left;
+    if (int rc = lse_poll(h)) return rc;
+    const bool bounded = lse_decide(h, !p.lp);
     p.bounded_lse = bounded ? 1 : 0;
-    h->last_decode_bounded = (bounded && !p.lp) ? 1 : 0;
     const int rows = h->B, nslabs = nslabs_of(rows, 4);
-    ScreenArgs sa{nullptr, nullptr, h->screen_scale, h->screen_ctr, h->screen_rounds};
-    const bool screen_on = h->screen_mode == 1 || (h->screen_mode == 2 && (int64_t)count * nslabs >= h->n_cu);
-    if (!coop_S && screen_on && !p.lp && bounded && h->screen_cap && h->screen_norm &&
-        (int64_t)count * nslabs <= h->screen_wgs) {         // screening is a property of the fused path
-        sa.cap = h->screen_cap;
-        sa.norm = h->screen_norm;
-    }
+    // (screening is a property of the fused path)
+    const ScreenArgs sa = pick_screen(h, count, (int64_t)count * nslabs, !coop_S && !p.lp && bounded);
     p.G = 4;
     p.S = coop_S ? coop_S : 1;
     p.part = h->part;
     p.coop = coop_S ? 1 : 0;
-    p.coop_launch = h->coop_launch;
     p.test_stall_ms = h->test_stall_left != 0 ? h->test_stall_ms : 0;
     if (p.coop && h->test_stall_ms && h->test_stall_left > 0) --h->test_stall_left;
     p.no_exit = (p.lp && nslabs > 1) ? 1 : 0;
@@ -2906,65 +2876,9 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
     p.B = rows;
     p.B_img = h->B;
     p.rpi = 1;
-    p.F = h->cfg.fc_feat_size;
-    p.V1 = h->V1;
-    p.T = h->cfg.seq_length;
-    p.D = h->D;
-    p.off_img_w = h->off[0];
-    p.off_img_b = h->off[1];
-    p.off_emb_w = h->off[2];
-    p.off_log_w = h->off[3];
-    p.off_log_b = h->off[4];
-    p.off_i2h_w = h->off[5];
-    p.off_i2h_b = h->off[6];
-    p.off_h2h_w = h->off[7];
-    p.off_h2h_b = h->off[8];
-    const size_t out_rows = (size_t)count * 2 * rows;
-    HIPC(h, hipMemsetAsync(p.seq, 0, out_rows * h->cfg.seq_length * sizeof(int32_t), s));
-    if (p.lp) HIPC(h, hipMemsetAsync(p.lp, 0, out_rows * h->cfg.seq_length * sizeof(float), s));
-    if (h->timing) HIPC(h, hipEventRecord(h->ev[0], s));
-    ParentArgs pa{es->ptab[es->cur], es->parent_of, es->Dp};
-    // the pairs in parts on the engine's streams when nicnes_set_decode_streams asks for it (as launch_decode_parts)
-    // (the coop launch needs all its workgroups resident: never split over streams)
-    const int nstr = p.coop ? 1 : std::min(count, std::max(h->dec_streams, 1));
-    if (nstr > 1) {
-        if (!h->ev_fork) HIPC(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        for (int i = 0; i < nstr - 1; ++i)
-            if (!h->sx[i]) {
-                HIPC(h, hipStreamCreateWithFlags(&h->sx[i], hipStreamNonBlocking));
-                HIPC(h, hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
-            }
-        HIPC(h, hipEventRecord(h->ev_fork, s));
-        for (int i = 0; i < nstr; ++i) {
-            const int a = (int)((int64_t)count * i / nstr), b = (int)((int64_t)count * (i + 1) / nstr);
-            DecodeParams pi = p;
-            ScreenArgs si_ = sa;
-            ParentArgs pai = pa;
-            nicnes_decode_shift(&pi, a, nslabs, nullptr, &si_, &pai);
-            hipStream_t si = i == 0 ? s : h->sx[i - 1];
-            if (i > 0) HIPC(h, hipStreamWaitEvent(si, h->ev_fork, 0));
-            HIPC(h, nicnes_launch_decode_es(&pi, &pai, b - a, nslabs, si, &si_));
-        }
-        for (int i = 0; i < nstr - 1; ++i) {
-            HIPC(h, hipEventRecord(h->ev_join[i], h->sx[i]));
-            HIPC(h, hipStreamWaitEvent(s, h->ev_join[i], 0));
-        }
-    } else {
-        HIPC(h, nicnes_launch_decode_es(&p, &pa, count, nslabs, s, &sa));
-    }
-    h->n_dev = 0;
-    h->multi_stream = nstr > 1;
-    if (p.lp) HIPC(h, nicnes_launch_lp_batch_exit(p.seq, p.lp, 2 * count, rows, h->cfg.seq_length, s));   // (as evaluate_impl)
-    if (h->timing) HIPC(h, hipEventRecord(h->ev[1], s));
-    if (!h->stats_pending) {
-        HIPC(h, hipMemcpyAsync(h->stats_host, h->stats, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIPC(h, hipEventRecord(h->stats_ev, s));
-        h->stats_pending = true;
-        h->last_bounded = bounded && !p.lp;
-    }
-    if (int rc = score_rollouts(h, p.seq, p.lp, 2 * count, rows, 1, mb, nullptr, fitness_out, nullptr, s)) return rc;
-    if (h->timing) HIPC(h, hipEventRecord(h->ev[2], s));
-    return NICNES_OK;
+    const ParentArgs pa{es->ptab[es->cur], es->parent_of, es->Dp};
+    return decode_and_score(h, p, MutHead{}, sa, nullptr, &pa, count, nslabs, (size_t)count * 2 * rows, 2 * count, rows, 1,
+                            mb, nullptr, fitness_out, nullptr, s);
 }
 
 }  // extern "C"
