@@ -232,6 +232,27 @@ int nicnes_split_score(nicnes_handle* h, nicnes_split* split, int32_t first, int
 int nicnes_split_evaluate(nicnes_handle* h, nicnes_split* split, int32_t first, int32_t count, int64_t* totals_out_dev,
                           double* metrics_out_dev, double* row_cider_out_dev, int32_t* seq_out, void* stream);
 
+/* Beam-search decode of the handle's current theta on images [first, first + count) of the split, for evaluation, in
+ * ONE enqueue with no host synchronisation (the work buffers grow with the largest (count, beam) seen, synchronising
+ * then). beam in 1..8 (else NICNES_ERR_INVALID). A hypothesis is an LSTM state, its tokens and an fp64 score; at every
+ * step the candidates (hypothesis b, word v) of an image, score_b + (double)logprob_b[v] with the greedy decode's
+ * log-probs, are ordered by (score descending, b ascending, v ascending) and the first min(beam, candidates) taken;
+ * one with v = 0, or taken at step seq_length, finishes, the others are the next step's hypotheses. The result is
+ * the finished hypothesis of the largest score (ties: finished at the earlier step, then earlier in selection
+ * order); an image stops once its best finished score is >= every live one. NO length normalisation is applied.
+ * beam = 1 is the greedy decode. seq_out [count, seq_length] int32 zero-padded; score_out (nullable) [count] fp64.
+ * One deviation from that order: each of a hypothesis's two vocabulary halves (ids with (v >> 2) even / odd) keeps its
+ * beam best words by LOGIT before the log-probs exist, so where a kept and a dropped logit of one half round to the
+ * same fp32 log-prob the larger logit is taken, not the smaller id (for beam = 1: the largest logit, where the greedy
+ * decode takes the first id of its log-prob tie window). An image whose logits are not finite finishes nothing: its
+ * tokens are zeros and its score -inf. */
+int nicnes_split_decode_beam(nicnes_handle* h, nicnes_split* split, int32_t first, int32_t count, int32_t beam,
+                             int32_t* seq_out, double* score_out, void* stream);
+/* nicnes_split_decode_beam + nicnes_split_score of its tokens; seq_out (nullable) receives them. */
+int nicnes_split_evaluate_beam(nicnes_handle* h, nicnes_split* split, int32_t first, int32_t count, int32_t beam,
+                               int64_t* totals_out_dev, double* metrics_out_dev, double* row_cider_out_dev,
+                               int32_t* seq_out, void* stream);
+
 /* A resident training set: every image of the training split on the GPU, so that an iteration's batches are drawn by
  * image index with device copies instead of being read, stacked and uploaded by the host (replaces what
  * src/captioning/dataloader.py:148-203 get_batch assembles and nic_nes_worker.py:121-128 hands to every member's
@@ -490,6 +511,16 @@ int nicnes_test_certify_items_owned(nicnes_handle* h, uint64_t iteration, int32_
 int nicnes_test_score_rows(nicnes_handle* h, const int32_t* seq_dev, int32_t n_cand, int32_t rows,
                            const int32_t* member_batch_host, const float* lp_dev, const double* base_dev,
                            double* scores_out_dev, double* fitness_out_dev, void* stream);
+
+/* The beam decode's workgroup shape: 4 or 8 waves, or 0 (the default) for the launch's own rule, which takes the shape
+ * that needs fewer rounds over the CUs. The tokens and scores do not depend on it; it exists for tests and timing. */
+int nicnes_set_beam_waves(nicnes_handle* h, int32_t waves);
+/* Test entry: the beam decode's own per-lane top-K and selection code on GIVEN rows. lp_dev [n_img, beam, V1] fp32
+ * log-probs, score_dev [n_img, beam] fp64, live_dev [n_img, beam] int32 (0: the hypothesis is dead and gives no
+ * candidate). out_dev [n_img, beam, 2] int32: the selected (b, v) pairs of every image in selection order, (-1, -1)
+ * where fewer than beam candidates exist. Any V1 >= 1; needs no theta. Asynchronous on stream. */
+int nicnes_test_beam_select(nicnes_handle* h, const float* lp_dev, const double* score_dev, const int32_t* live_dev,
+                            int32_t n_img, int32_t beam, int32_t V1, int32_t* out_dev, void* stream);
 
 /* ---- nic_es: the truncation-selection GA (src/algorithm/nic_es/) ----------------------------------------------------
  * The reference keeps every parent, offspring and elite as a .pth file on a shared disk (11.46 MB each). Here a parent

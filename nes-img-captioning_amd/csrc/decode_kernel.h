@@ -173,5 +173,18 @@ extern "C" hipError_t nicnes_launch_test_logit_chain(const DecodeParams* p, uint
 extern "C" hipError_t nicnes_launch_test_certify_items(const DecodeParams* p, uint64_t nidx, int sgn, const float* hin,
                                                        const int32_t* lane_start, const int32_t* ids,
                                                        const int32_t* pos_of, float* out, hipStream_t stream);
+// beam-search decode (beam_kernels.hip) of theta over `count` images from p->fc, beam width K in 1..8, one launch: seq
+// [count, T] and score [count] (the fp64 sum of the winner's log-probs); reads theta, fc, F, V1, T, D and the offsets
+// of *p. xscr: nicnes_beam_scratch_floats(count, K) floats of lane-private scratch.
+extern "C" size_t nicnes_beam_scratch_floats(int count, int K);
+// n_cu: the device's CUs (the launch takes 4-wave workgroups instead of 8-wave ones while that costs fewer rounds);
+// force_nw: 4 or 8 waves per workgroup whatever the range (nicnes_set_beam_waves), 0 the rule
+extern "C" int nicnes_beam_waves_per_wg(int count, int K, int n_cu);
+extern "C" hipError_t nicnes_launch_beam_decode(const DecodeParams* p, int32_t* seq, double* score, float* xscr, int count,
+                                                int K, int n_cu, int force_nw, hipStream_t stream);
+// test entry (nicnes_test_beam_select): the decode's per-lane top-K and selection over given log-prob rows
+// [n_img, K, V1], scores and live flags [n_img, K]; out [n_img, K, 2] (row of the image, id), pre-filled with -1
+extern "C" hipError_t nicnes_launch_test_beam_select(const float* lp, const double* score, const int32_t* live, int n_img,
+                                                     int K, int V1, int32_t* out, hipStream_t stream);
 // lane scratch for up to member_count members x row_waves 32-row waves of one sign
 extern "C" size_t nicnes_decode_scratch_floats(int member_count, int row_waves_per_member);

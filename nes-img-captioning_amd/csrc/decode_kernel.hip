@@ -3783,6 +3783,9 @@ extern "C" hipError_t nicnes_launch_test_logit_chain(const DecodeParams* p, uint
     return hipGetLastError();
 }
 
+// the beam-search decode (evaluation only): its kernels and launches, compiled in this unit ahead of its last kernel
+#include "beam_kernels.hip"
+
 // ========== test entry: given (row, id) items through the screened decode's certify_tiles ======================
 // One workgroup of the decode's shape. hin [128, 128] is laid out as its eight waves' lane scratch (wave w: sign w >> 2,
 // rows 32 (w & 3) .. + 31, both signs the same rows), from where the waves of sign sgn load their B operand as step_body

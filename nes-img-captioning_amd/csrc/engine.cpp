@@ -132,6 +132,7 @@ struct nicnes_handle {
     size_t rank_cap = 0;
     int64_t part_cap = 0;             // in logit workgroups (members x slabs x S)
     int n_cu = 256;
+    int beam_waves = 0;               // nicnes_set_beam_waves: 4 or 8 waves per beam-decode workgroup, 0 the launch's rule
     int dec_S = 0, dec_G = 0;         // nicnes_set_decode_split (0 = automatic)
     // the decode's members in n parts on n streams (nicnes_set_decode_streams, NICNES_DECODE_STREAMS;
     // 0 = automatic: 2 on the split path, 1 on the fused path): one part's launches fill the CUs the
@@ -263,6 +264,13 @@ struct nicnes_split {
     uint64_t* zero_idx = nullptr;
     int32_t* block = nullptr;
     float* part = nullptr;
+    // beam decode work (nicnes_split_decode_beam), grown to the largest (count, beam) seen: tokens and scores of
+    // beam_rows images, beam_scr floats of lane-private scratch
+    int32_t beam_rows = 0;
+    size_t beam_scr = 0;
+    int32_t* beam_seq = nullptr;
+    double* beam_score = nullptr;
+    float* beam_xscr = nullptr;
 };
 
 // A resident training set (nicnes_trainset_create): every training image's fc row and raw reference rows on the
@@ -1607,7 +1615,8 @@ int nicnes_evaluate_theta(nicnes_handle* h, int32_t batch, uint64_t iteration, d
 static void split_free(nicnes_split* sp) {
     void* bufs[] = {sp->fc, sp->ref_tokens, sp->img_ref_start, sp->hash_keys, sp->hash_vals, sp->ref_keys, sp->ref_vec,
                     sp->ref_count, sp->ref_len2, sp->ref_norm, sp->img_stats, sp->img_rouge, sp->img_cider, sp->seq, sp->lp,
-                    sp->scratch, sp->alive, sp->coop_ctr, sp->zero_idx, sp->block, sp->part};
+                    sp->scratch, sp->alive, sp->coop_ctr, sp->zero_idx, sp->block, sp->part, sp->beam_seq, sp->beam_score,
+                    sp->beam_xscr};
     for (void* q : bufs)
         if (q) (void)hipFree(q);
     delete sp;
@@ -1875,6 +1884,94 @@ int nicnes_split_evaluate(nicnes_handle* h, nicnes_split* sp, int32_t first, int
     if (int rc = split_decode_impl(h, sp, first, count, seq_out, nullptr, (hipStream_t)stream, &seq)) return rc;
     return split_score_impl(h, sp, first, count, seq, totals_out_dev, metrics_out_dev, row_cider_out_dev,
                             (hipStream_t)stream);
+}
+
+// ---- beam-search decode of a split (evaluation only; beam_kernels.hip) ------------------------------------------------
+static int split_beam_grow(nicnes_handle* h, nicnes_split* sp, int32_t count, int32_t beam) {
+    const size_t T = (size_t)h->cfg.seq_length;
+    if (count > sp->beam_rows) {
+        HIPC(h, hipDeviceSynchronize());
+        if (sp->beam_seq) (void)hipFree(sp->beam_seq);
+        if (sp->beam_score) (void)hipFree(sp->beam_score);
+        sp->beam_seq = nullptr; sp->beam_score = nullptr;
+        sp->beam_rows = 0;
+        int rc = dalloc(h, &sp->beam_seq, (size_t)count * T);
+        if (!rc) rc = dalloc(h, &sp->beam_score, (size_t)count);
+        if (rc) return rc;
+        sp->beam_rows = count;
+    }
+    const size_t need = nicnes_beam_scratch_floats(count, beam);
+    if (need > sp->beam_scr) {
+        HIPC(h, hipDeviceSynchronize());
+        if (sp->beam_xscr) (void)hipFree(sp->beam_xscr);
+        sp->beam_xscr = nullptr;
+        sp->beam_scr = 0;
+        int rc = dalloc(h, &sp->beam_xscr, need);
+        if (rc) return rc;
+        sp->beam_scr = need;
+    }
+    return NICNES_OK;
+}
+
+// The beam decode of theta on images [first, first + count) in one enqueue. *seq_dev: the tokens in the split's own
+// buffer [count, T]; seq_out / score_out (nullable) receive copies.
+static int split_decode_beam_impl(nicnes_handle* h, nicnes_split* sp, int32_t first, int32_t count, int32_t beam,
+                                  int32_t* seq_out, double* score_out, hipStream_t s, const int32_t** seq_dev) {
+    if (!split_of(h, sp)) return fail(h, NICNES_ERR_INVALID, "not a split of this handle");
+    if (beam < 1 || beam > 8) return fail(h, NICNES_ERR_INVALID, "beam out of [1, 8]");
+    if (first < 0 || count < 1 || (int64_t)first + count > sp->N)
+        return fail(h, NICNES_ERR_INVALID, "range outside the split's images");
+    if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
+    HIPC(h, hipSetDevice(h->device));
+    if (int rc = split_beam_grow(h, sp, count, beam)) return rc;
+    const size_t T = (size_t)h->cfg.seq_length;
+    DecodeParams p = decode_base(h);
+    p.theta = h->theta32;
+    p.fc = sp->fc + (size_t)first * h->cfg.fc_feat_size;
+    HIPC(h, nicnes_launch_beam_decode(&p, sp->beam_seq, sp->beam_score, sp->beam_xscr, count, beam, h->n_cu,
+                                      h->beam_waves, s));
+    if (seq_out)
+        HIPC(h, hipMemcpyAsync(seq_out, sp->beam_seq, (size_t)count * T * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (score_out)
+        HIPC(h, hipMemcpyAsync(score_out, sp->beam_score, (size_t)count * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (seq_dev) *seq_dev = sp->beam_seq;
+    return NICNES_OK;
+}
+
+int nicnes_split_decode_beam(nicnes_handle* h, nicnes_split* sp, int32_t first, int32_t count, int32_t beam,
+                             int32_t* seq_out, double* score_out, void* stream) {
+    if (!h || !sp || !seq_out) return NICNES_ERR_INVALID;
+    return split_decode_beam_impl(h, sp, first, count, beam, seq_out, score_out, (hipStream_t)stream, nullptr);
+}
+
+int nicnes_split_evaluate_beam(nicnes_handle* h, nicnes_split* sp, int32_t first, int32_t count, int32_t beam,
+                               int64_t* totals_out_dev, double* metrics_out_dev, double* row_cider_out_dev,
+                               int32_t* seq_out, void* stream) {
+    if (!h || !sp || !totals_out_dev || !metrics_out_dev) return NICNES_ERR_INVALID;
+    if (split_of(h, sp) && sp->n_refs == 0)
+        return fail(h, NICNES_ERR_INVALID, "a decode-only split has no references to score against");
+    const int32_t* seq = nullptr;
+    if (int rc = split_decode_beam_impl(h, sp, first, count, beam, seq_out, nullptr, (hipStream_t)stream, &seq)) return rc;
+    return split_score_impl(h, sp, first, count, seq, totals_out_dev, metrics_out_dev, row_cider_out_dev,
+                            (hipStream_t)stream);
+}
+
+int nicnes_set_beam_waves(nicnes_handle* h, int32_t waves) {
+    if (!h || (waves != 0 && waves != 4 && waves != 8)) return NICNES_ERR_INVALID;
+    h->beam_waves = waves;
+    return NICNES_OK;
+}
+
+int nicnes_test_beam_select(nicnes_handle* h, const float* lp_dev, const double* score_dev, const int32_t* live_dev,
+                            int32_t n_img, int32_t beam, int32_t V1, int32_t* out_dev, void* stream) {
+    if (!h || !lp_dev || !score_dev || !live_dev || !out_dev) return NICNES_ERR_INVALID;
+    if (beam < 1 || beam > 8) return fail(h, NICNES_ERR_INVALID, "beam out of [1, 8]");
+    if (n_img < 1 || V1 < 1) return fail(h, NICNES_ERR_INVALID, "n_img and V1 must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipMemsetAsync(out_dev, 0xff, (size_t)n_img * beam * 2 * sizeof(int32_t), s));
+    HIPC(h, nicnes_launch_test_beam_select(lp_dev, score_dev, live_dev, n_img, beam, V1, out_dev, s));
+    return NICNES_OK;
 }
 
 int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, float* out, void* stream) {

@@ -27,6 +27,7 @@ EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_create', 'nicne
            'nicnes_test_certify_items', 'nicnes_test_certify_items_owned',
            'nicnes_set_decode_screen', 'nicnes_set_decode_queue', 'nicnes_decode_queue_plan', 'nicnes_screen_stats', 'nicnes_screen_reasons', 'nicnes_split_create', 'nicnes_split_destroy',
            'nicnes_split_decode', 'nicnes_split_score', 'nicnes_split_evaluate',
+           'nicnes_split_decode_beam', 'nicnes_split_evaluate_beam', 'nicnes_test_beam_select', 'nicnes_set_beam_waves',
            'nicnes_es_create', 'nicnes_es_free', 'nicnes_es_set_mutation', 'nicnes_es_set_parent',
            'nicnes_es_set_parent_count', 'nicnes_es_get_row', 'nicnes_es_row_stats', 'nicnes_es_evaluate',
            'nicnes_es_offspring', 'nicnes_es_select', 'nicnes_es_advance', 'nicnes_es_set_elite',
@@ -121,6 +122,10 @@ def lib(path=None):
         'nicnes_split_decode': (c.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         'nicnes_split_score': (c.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
         'nicnes_split_evaluate': (c.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+        'nicnes_split_decode_beam': (c.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
+        'nicnes_split_evaluate_beam': (c.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+        'nicnes_test_beam_select': (c.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+        'nicnes_set_beam_waves': (c.c_int, [vp, i32]),
         'nicnes_trainset_create': (c.c_int, [vp, vp, i32, vp, i32, vp, c.POINTER(vp), vp]),
         'nicnes_trainset_write_fc': (c.c_int, [vp, vp, i32, i32, vp, vp]),
         'nicnes_trainset_destroy': (c.c_int, [vp, vp]),

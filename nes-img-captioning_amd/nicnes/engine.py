@@ -540,6 +540,29 @@ class Engine:
             torch.cuda.current_stream().synchronize()   # the inputs stay alive until the kernels have read them
         return scores, fit
 
+    def set_beam_waves(self, waves=0):
+        """The beam decode's workgroup shape: 4 or 8 waves, 0 the launch's own rule (results do not depend on it)."""
+        check(self.L.nicnes_set_beam_waves(self.h, int(waves)), self.h, 'set_beam_waves')
+
+    def test_beam_select(self, lp, score, live):
+        """Test entry: the beam decode's own top-K and selection code on given rows. lp [n_img, K, V1] fp32 log-probs,
+        score [n_img, K] fp64, live [n_img, K] (0: dead). Returns int32 [n_img, K, 2] on the GPU: every image's
+        selected (b, v) pairs in selection order, (-1, -1) where fewer than K candidates exist (synchronises)."""
+        lp_t = self._dev(lp, torch.float32)
+        if lp_t.dim() != 3:
+            raise ValueError('lp must be [n_img, K, V1]')
+        n_img, K, V1 = (int(x) for x in lp_t.shape)
+        sc_t = self._dev(score, torch.float64)
+        lv_t = self._dev(live, torch.int32)
+        if tuple(sc_t.shape) != (n_img, K) or tuple(lv_t.shape) != (n_img, K):
+            raise ValueError('score and live must be [n_img, K]')
+        out = torch.empty((n_img, K, 2), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_test_beam_select(self.h, _ptr(lp_t), _ptr(sc_t), _ptr(lv_t), n_img, K, V1, _ptr(out),
+                                                 self._stream()), self.h, 'test_beam_select')
+            torch.cuda.current_stream().synchronize()   # the inputs stay alive until the kernel has read them
+        return out
+
     def decode_path(self, B=None, count=1):
         """'fused', 'split' or 'coop': the decode path an evaluate of `count` members would take."""
         out = ctypes.c_int32()
@@ -844,6 +867,28 @@ class Split:
                   'split_decode')
         return (seq, lp) if return_lp else seq
 
+    @staticmethod
+    def _beam(beam_size):
+        beam = int(beam_size)
+        if beam < 1 or beam > 8:
+            raise ValueError('beam_size must be in 1..8, got %r' % (beam_size,))
+        return beam
+
+    def decode_beam(self, first=0, count=None, beam_size=3, return_score=False):
+        """Beam-search tokens [count, T] int32 (zero-padded) of the engine's current theta on images [first, first +
+        count), in one enqueue: the finished hypothesis with the largest sum of log-probs, beam_size in 1..8, NO
+        length normalisation (nicnes_split_decode_beam). return_score adds that sum, [count] fp64. beam_size = 1 is
+        the greedy decode."""
+        e = self.engine
+        beam = self._beam(beam_size)
+        first, count = self._range(first, count)
+        seq = torch.empty((count, e.cfg.seq_length), dtype=torch.int32, device=e.device)
+        score = torch.empty(count, dtype=torch.float64, device=e.device) if return_score else None
+        with torch.cuda.device(e.device):
+            check(e.L.nicnes_split_decode_beam(e.h, self.sp, first, count, beam, _ptr(seq), _ptr(score), e._stream()),
+                  e.h, 'split_decode_beam')
+        return (seq, score) if return_score else seq
+
     def _outputs(self, count, rows):
         e = self.engine
         return (torch.empty(10, dtype=torch.int64, device=e.device), torch.empty(6, dtype=torch.float64, device=e.device),
@@ -875,15 +920,21 @@ class Split:
             torch.cuda.current_stream().synchronize()    # sq stays alive until the kernels have read it
         return self._result(totals, metrics, rows, detail)
 
-    def evaluate(self, first=0, count=None, detail=False, return_seq=False):
-        """decode + score in one call: COCOEvalCap's dict for the engine's current theta on the split."""
+    def evaluate(self, first=0, count=None, detail=False, return_seq=False, beam_size=None):
+        """decode + score in one call: COCOEvalCap's dict for the engine's current theta on the split. beam_size
+        (1..8) decodes with decode_beam instead of greedily; None is the greedy path itself."""
         e = self.engine
+        beam = None if beam_size is None else self._beam(beam_size)
         first, count = self._range(first, count)
         totals, metrics, rows = self._outputs(count, detail)
         seq = torch.empty((count, e.cfg.seq_length), dtype=torch.int32, device=e.device) if return_seq else None
         with torch.cuda.device(e.device):
-            check(e.L.nicnes_split_evaluate(e.h, self.sp, first, count, _ptr(totals), _ptr(metrics), _ptr(rows),
-                                            _ptr(seq), e._stream()), e.h, 'split_evaluate')
+            if beam is None:
+                check(e.L.nicnes_split_evaluate(e.h, self.sp, first, count, _ptr(totals), _ptr(metrics), _ptr(rows),
+                                                _ptr(seq), e._stream()), e.h, 'split_evaluate')
+            else:
+                check(e.L.nicnes_split_evaluate_beam(e.h, self.sp, first, count, beam, _ptr(totals), _ptr(metrics),
+                                                     _ptr(rows), _ptr(seq), e._stream()), e.h, 'split_evaluate_beam')
         res = self._result(totals, metrics, rows, detail)
         return (res, seq) if return_seq else res
 

@@ -6,7 +6,8 @@ eval_on_test.py (CaptPolicy.accuracy_on -> eval_split, captioning/eval_utils.py:
 
 Writes {'stats': {'Bleu_1'..'Bleu_4', 'ROUGE_L', 'CIDEr'}, 'predictions': [{'image_id', 'caption'}]} as JSON. The
 metrics are computed on the split's label rows (word ids, captions cut to seq_length words, rare words as UNK), not
-on PTB-tokenised raw annotations; METEOR and SPICE (java) are not computed (nicnes.validation).
+on PTB-tokenised raw annotations; METEOR and SPICE (java) are not computed (nicnes.validation). --beam_size K (1..8)
+decodes with the engine's beam search (sum of log-probs, no length normalisation) instead of greedily.
 """
 import argparse
 import importlib
@@ -22,6 +23,8 @@ def parse_args(argv=None):
     ap.add_argument('--num', type=int, default=None, help='images (default config.num_val_items; -1: the whole split)')
     ap.add_argument('--out', required=True)
     ap.add_argument('--incl_gts', action='store_true', help='add the reference captions to every prediction')
+    ap.add_argument('--beam_size', type=int, default=None, choices=range(1, 9), metavar='K',
+                    help='beam width 1..8 of the decode (default: greedy)')
     ap.add_argument('--data_root', default='.', help="directory the caption_options paths are relative to")
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--engine_factory', default=None, help='module:function(spec, args) -> engine (default: an Engine)')
@@ -49,7 +52,7 @@ def main(argv=None):
         engine = default_engine(spec, args)
     EnginePolicy(engine).set_model(args.model)
     num = args.num if args.num is not None else spec.config.num_val_items
-    validator = Validator(engine, loader, args.split, 5000 if num is None else int(num))
+    validator = Validator(engine, loader, args.split, 5000 if num is None else int(num), beam_size=args.beam_size)
     stats, predictions = validator.eval_split(incl_gts=args.incl_gts)
     with open(args.out, 'w') as f:
         json.dump({'stats': stats, 'predictions': predictions}, f)

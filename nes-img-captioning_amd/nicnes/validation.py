@@ -70,9 +70,15 @@ class Validator:
 
     loader: nicnes.data.CocoFcDataLoader, or any object with split_ix[split] (image indices), info['images'][ix]['id'],
     ix_to_word, seq_length, fc_feature(ix) -> [F] and labels (a LabelStore: every label row of image ix is
-    labels.labels[label_start_ix[ix] - 1 : label_end_ix[ix]], the gts of get_batch)."""
+    labels.labels[label_start_ix[ix] - 1 : label_end_ix[ix]], the gts of get_batch).
 
-    def __init__(self, engine, loader, split='val', num=5000):
+    beam_size (1..8; None: greedy, the reference's eval during training) decodes with the engine's beam search
+    (Split.decode_beam: the sum of log-probs, no length normalisation), as test-time evaluation usually does."""
+
+    def __init__(self, engine, loader, split='val', num=5000, beam_size=None):
+        if beam_size is not None and not 1 <= int(beam_size) <= 8:
+            raise ValueError('beam_size must be in 1..8, got %r' % (beam_size,))
+        self.beam_size = None if beam_size is None else int(beam_size)
         self.engine = engine
         self.loader = loader
         ixs = list(loader.split_ix[split])
@@ -91,7 +97,7 @@ class Validator:
     def eval_split(self, incl_gts=False):
         """(lang_stats, predictions): COCOEvalCap's dict and [{'image_id', 'caption'}] in split order; incl_gts adds
         the reference strings as 'gts'."""
-        stats, seq = self.split.evaluate(return_seq=True)
+        stats, seq = self.split.evaluate(return_seq=True, **self._beam())
         seq = seq.cpu().numpy() if hasattr(seq, 'cpu') else np.asarray(seq)
         sents = decode_sequence(self.loader.ix_to_word, seq)
         preds = []
@@ -104,7 +110,11 @@ class Validator:
 
     def accuracy(self):
         """CaptPolicy.accuracy_on: the CIDEr of eval_split."""
-        return float(self.split.evaluate()['CIDEr'])
+        return float(self.split.evaluate(**self._beam())['CIDEr'])
+
+    def _beam(self):
+        """the decode's keyword: none at all for the greedy path (an engine without a beam decode still validates)"""
+        return {} if self.beam_size is None else {'beam_size': self.beam_size}
 
     def close(self):
         self.split.close()
