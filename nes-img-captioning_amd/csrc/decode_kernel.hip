@@ -3505,6 +3505,7 @@ extern "C" void nicnes_decode_shift(DecodeParams* p, int m0, int nslabs, MutHead
     if (pa && pa->parent_of) pa->parent_of += m0;
     p->seq += rows;
     if (p->lp) p->lp += rows;
+    if (p->sample_u) p->sample_u += rows;                        // the draws [member][2][B][T], laid out as seq
     p->scratch += wg0 * (size_t)(2 * p->G) * (SCR_SLOTS * 64);   // make_ctx / make_sctx lane scratch
     p->alive += wg0;
     p->alive2 += wg0;
