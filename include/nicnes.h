@@ -536,8 +536,35 @@ int nicnes_es_free(nicnes_handle* h);
 /* ES mutation (PolicyNet.evolve with the parent as param_vector, src/algorithm/nets.py:96-113): NICNES_MUTATION_PLAIN,
  * or NICNES_MUTATION_SCALE = SM-PROPORTIONAL, delta'[j] = fp32(fp32(sigma z[j]) * a[j]) with a[j] = |theta_p[j]|, or
  * mean|theta_p| where theta_p[j] is exactly 0; the mean is the engine's (fp32 of an fp64 sum in a fixed order, formed
- * when the row is written). SM-G-SUM / SM-VECTOR: NICNES_ERR_UNSUPPORTED. Independent of nicnes_set_mutation. */
+ * when the row is written). Any other mode, NICNES_MUTATION_DIVIDE included (it is set by
+ * nicnes_set_mutation_divide_es): NICNES_ERR_UNSUPPORTED. Independent of nicnes_set_mutation. */
 int nicnes_es_set_mutation(nicnes_handle* h, int32_t mode);
+/* The ES mutation becomes NICNES_MUTATION_DIVIDE = SM-G-SUM / SM-VECTOR, delta'[j] = fp32(fp32(sigma z[j]) / s_p[j])
+ * (IEEE division, the arithmetic of nicnes_set_mutation's divide) with s_p the sensitivity of the pair's own parent
+ * (nicnes_sensitivity_es, nicnes_set_sensitivity_es). nicnes_es_evaluate, nicnes_es_offspring and nicnes_es_advance
+ * then fail with NICNES_ERR_INVALID, before anything is enqueued, when a parent they name has no valid sensitivity
+ * (nicnes_es_advance checks every entry of parent_of_host: the survivors are known only on the device).
+ * nicnes_es_set_mutation leaves the mode again. */
+int nicnes_set_mutation_divide_es(nicnes_handle* h);
+/* The SM-G-SUM sensitivity of each named slot of the CURRENT parent table (Sensitivity.calc_sensitivity, cached by the
+ * reference per (task_id, parent_id), safe_mutations.py:34-84): what nicnes_sum_sensitivity computes for the handle's
+ * theta (the same kernels, on the first `rows` images of the batch held, with the underflow clamp), for
+ * theta = parent row slot, into row slot of a sensitivity table [max_parents, Dp] fp32, which becomes valid. The slots
+ * run one after the other on `stream`. slots_host [n_slots] (HOST). The table is allocated at the first call
+ * (synchronising then; its pad columns [D, Dp) are written 1.0 once); afterwards the call only enqueues.
+ * NICNES_ERR_INVALID: a slot outside [0, parent count), rows outside [1, B], underflow <= 0, no batch held.
+ * A row stops being valid when nicnes_es_set_parent rewrites its slot, and every row does at nicnes_es_advance (the
+ * tables swap). Leaves shared mode (below). */
+int nicnes_sensitivity_es(nicnes_handle* h, const int32_t* slots_host, int32_t n_slots, int32_t rows, float underflow,
+                          void* stream);
+/* slot >= 0: row `slot` of the sensitivity table <- vec_dev [D] fp32 (device), valid from then (tests, resuming).
+ * slot = -1: vec_dev is ONE vector every parent shares (SM-VECTOR, Sensitivity.set_sensitivity): the handle keeps one
+ * copy, which the kernels read with row stride 0, and which stays valid over nicnes_es_set_parent and
+ * nicnes_es_advance, until a per-parent call (this one with slot >= 0, or nicnes_sensitivity_es) leaves shared mode. */
+int nicnes_set_sensitivity_es(nicnes_handle* h, int32_t slot, const float* vec_dev, void* stream);
+/* out_dev [D] fp32 (device) <- the slot's sensitivity row, or the shared vector for any slot in shared mode.
+ * NICNES_ERR_INVALID when the slot has none. */
+int nicnes_get_sensitivity_es(nicnes_handle* h, int32_t slot, float* out_dev, void* stream);
 /* Parent row `slot` of the current table <- theta32 [D] fp32 (device), and its statistics; the parent count is set
  * apart (slots [0, count) are the parents an evaluate may name). Replaces ESIteration.init_parents / the parent paths
  * of ESTask (nic_es_master.py:27-34). */

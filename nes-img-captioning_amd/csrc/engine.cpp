@@ -212,7 +212,12 @@ struct nicnes_es {
     int32_t max_parents = 0, max_elites = 0, n_parents = 0;
     int64_t Dp = 0;
     int cur = 0;
-    int mode = 0;                     // NICNES_MUTATION_PLAIN or _SCALE
+    int mode = 0;                     // NICNES_MUTATION_PLAIN, _SCALE or _DIVIDE
+    float* stab = nullptr;            // [max_parents, Dp] the current parents' sensitivity rows (nicnes_sensitivity_es;
+                                      // allocated at the first use, pad columns 1.0)
+    float* svec = nullptr;            // [Dp] the vector every parent shares (nicnes_set_sensitivity_es, slot -1)
+    bool sens_shared = false;         // DIVIDE reads svec with row stride 0, not stab
+    std::vector<uint8_t> sens_valid;  // [max_parents] row p of stab belongs to row p of ptab[cur]
     float* ptab[2] = {nullptr, nullptr};
     float* etab = nullptr;
     float* pmean[2] = {nullptr, nullptr};   // [max_parents] mean|theta_p| of the tables' rows
@@ -1974,13 +1979,9 @@ int nicnes_test_beam_select(nicnes_handle* h, const float* lp_dev, const double*
     return NICNES_OK;
 }
 
-int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, float* out, void* stream) {
-    if (!h || !out || rows < 1) return NICNES_ERR_INVALID;
-    if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
-    if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
-    if (rows > h->B) return fail(h, NICNES_ERR_INVALID, "rows beyond the batch held");
-    hipStream_t s = (hipStream_t)stream;
-    HIPC(h, hipSetDevice(h->device));
+// The SM-G-SUM sensitivity of `theta` (the handle's theta32, or a parent row of nicnes_sensitivity_es) on the first
+// `rows` images of the batch held, into out [D]
+static int sens_of_theta(nicnes_handle* h, const float* theta, int32_t rows, float underflow, float* out, hipStream_t s) {
     const int L = 5, split = 100;                                  // forward_for_sensitivity defaults (nets.py:22)
     if (!h->sens_tok) {
         HIPC(h, hipDeviceSynchronize());
@@ -1989,7 +1990,7 @@ int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, floa
         h->sens = nicnes_sens_create();
     }
     SensParams sp;
-    sp.theta = h->theta32;
+    sp.theta = theta;
     sp.fc = h->fc;
     sp.tok = h->sens_tok;                                          // [rows, L - 1], written by the forward
     sp.tok_stride = L - 1;
@@ -2011,6 +2012,15 @@ int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, floa
     const int rc = nicnes_sens_run(h->sens, &sp, s);
     if (rc) return fail(h, NICNES_ERR_HIP, "sensitivity kernels failed (code " + std::to_string(rc) + ")");
     return NICNES_OK;
+}
+
+int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, float* out, void* stream) {
+    if (!h || !out || rows < 1) return NICNES_ERR_INVALID;
+    if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
+    if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
+    if (rows > h->B) return fail(h, NICNES_ERR_INVALID, "rows beyond the batch held");
+    HIPC(h, hipSetDevice(h->device));
+    return sens_of_theta(h, h->theta32, rows, underflow, out, (hipStream_t)stream);
 }
 
 int nicnes_rank_weights(nicnes_handle* h, const double* fitness, int32_t P, double* cr_out, float* w_out, void* stream) {
@@ -2582,7 +2592,8 @@ int nicnes_es_free(nicnes_handle* h) {
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     void* bufs[] = {es->ptab[0], es->ptab[1], es->etab, es->pmean[0], es->pmean[1], es->pzero[0], es->pzero[1], es->emean,
-                    es->ezero, es->part_sum, es->part_zero, es->parent_of, es->neg, es->dbuf, es->didx, es->gat};
+                    es->ezero, es->part_sum, es->part_zero, es->parent_of, es->neg, es->dbuf, es->didx, es->gat, es->stab,
+                    es->svec};
     for (void* q : bufs)
         if (q) (void)hipFree(q);
     delete es;
@@ -2599,6 +2610,7 @@ int nicnes_es_create(nicnes_handle* h, int32_t max_parents, int32_t max_elites) 
     es->max_parents = max_parents;
     es->max_elites = max_elites;
     es->Dp = (h->D + 63) / 64 * 64;
+    es->sens_valid.assign((size_t)max_parents, 0);
     const size_t MP = (size_t)max_parents, ME = (size_t)max_elites, MM = (size_t)h->cfg.max_members;
     int rc = NICNES_OK;
     for (int t = 0; t < 2 && !rc; ++t) {
@@ -2638,8 +2650,16 @@ int nicnes_es_create(nicnes_handle* h, int32_t max_parents, int32_t max_elites) 
 int nicnes_es_set_mutation(nicnes_handle* h, int32_t mode) {
     ES_STATE(h);
     if (mode != NICNES_MUTATION_PLAIN && mode != NICNES_MUTATION_SCALE)
-        return fail(h, NICNES_ERR_UNSUPPORTED, "nic_es mutation: the engine implements plain and SM-PROPORTIONAL");
+        return fail(h, NICNES_ERR_UNSUPPORTED,
+                    "nic_es mutation: this entry sets plain and SM-PROPORTIONAL (the divide of SM-G-SUM / SM-VECTOR, which "
+                    "needs the parents' sensitivities: nicnes_set_mutation_divide_es)");
     es->mode = mode;
+    return NICNES_OK;
+}
+
+int nicnes_set_mutation_divide_es(nicnes_handle* h) {
+    ES_STATE(h);
+    es->mode = NICNES_MUTATION_DIVIDE;
     return NICNES_OK;
 }
 
@@ -2649,6 +2669,7 @@ int nicnes_es_set_parent(nicnes_handle* h, int32_t slot, const float* theta32, v
     hipStream_t s = (hipStream_t)stream;
     HIPC(h, hipSetDevice(h->device));
     float* row = es->ptab[es->cur] + (size_t)slot * (size_t)es->Dp;
+    es->sens_valid[(size_t)slot] = 0;  // the slot's sensitivity row was another theta's
     HIPC(h, hipMemcpyAsync(row, theta32, (size_t)h->D * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIPC(h, nicnes_launch_es_parent_stats(row, 1, es->Dp, h->D, es->part_sum, es->part_zero, es->pmean[es->cur] + slot,
                                           es->pzero[es->cur] + slot, s));
@@ -2659,6 +2680,92 @@ int nicnes_es_set_parent_count(nicnes_handle* h, int32_t count) {
     ES_STATE(h);
     if (count < 1 || count > es->max_parents) return fail(h, NICNES_ERR_INVALID, "parent count out of [1, max_parents]");
     es->n_parents = count;
+    return NICNES_OK;
+}
+
+// ---- the parents' sensitivities (NICNES_MUTATION_DIVIDE: SM-G-SUM, SM-VECTOR) ----
+// The table [max_parents, Dp], allocated at the first use (synchronising then), the pad columns written 1.0 once.
+static int es_sens_table(nicnes_handle* h, nicnes_es* es, hipStream_t s) {
+    if (es->stab) return NICNES_OK;
+    HIPC(h, hipDeviceSynchronize());
+    if (int rc = dalloc(h, &es->stab, (size_t)es->max_parents * (size_t)es->Dp)) return rc;
+    HIPC(h, nicnes_launch_es_sens_pad(es->stab, es->max_parents, es->Dp, h->D, s));
+    return NICNES_OK;
+}
+
+// DIVIDE needs a sensitivity for every parent a call names: the shared vector, or a valid row per slot. Checked on the
+// host before anything is enqueued (n slots, each also checked against the parent count).
+static int es_sens_ready(nicnes_handle* h, const nicnes_es* es, const int32_t* slots, int n) {
+    if (es->mode != NICNES_MUTATION_DIVIDE || es->sens_shared) return NICNES_OK;
+    for (int k = 0; k < n; ++k) {
+        const int32_t p = slots[k];
+        if (p < 0 || p >= es->n_parents) return fail(h, NICNES_ERR_INVALID, "parent_of entry out of range");
+        if (!es->stab || !es->sens_valid[(size_t)p])
+            return fail(h, NICNES_ERR_INVALID, "divide mutation: parent " + std::to_string(p) +
+                                                   " has no valid sensitivity (nicnes_sensitivity_es / "
+                                                   "nicnes_set_sensitivity_es after the parents were written)");
+    }
+    return NICNES_OK;
+}
+
+int nicnes_sensitivity_es(nicnes_handle* h, const int32_t* slots_host, int32_t n_slots, int32_t rows, float underflow,
+                          void* stream) {
+    ES_STATE(h);
+    if (!slots_host || n_slots < 1) return NICNES_ERR_INVALID;
+    if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
+    if (rows < 1 || rows > h->B) return fail(h, NICNES_ERR_INVALID, "rows out of [1, B] of the batch held");
+    if (!(underflow > 0.f)) return fail(h, NICNES_ERR_INVALID, "underflow must be > 0 (calc_sensitivity divides by it)");
+    for (int k = 0; k < n_slots; ++k)
+        if (slots_host[k] < 0 || slots_host[k] >= es->n_parents)
+            return fail(h, NICNES_ERR_INVALID, "sensitivity slot outside [0, parent count)");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    if (int rc = es_sens_table(h, es, s)) return rc;
+    es->sens_shared = false;
+    for (int k = 0; k < n_slots; ++k) {            // one parent after the other on the caller's stream
+        const size_t at = (size_t)slots_host[k] * (size_t)es->Dp;
+        es->sens_valid[(size_t)slots_host[k]] = 0;
+        if (int rc = sens_of_theta(h, es->ptab[es->cur] + at, rows, underflow, es->stab + at, s)) return rc;
+        es->sens_valid[(size_t)slots_host[k]] = 1;
+    }
+    return NICNES_OK;
+}
+
+int nicnes_set_sensitivity_es(nicnes_handle* h, int32_t slot, const float* vec_dev, void* stream) {
+    ES_STATE(h);
+    if (!vec_dev || slot < -1 || slot >= es->max_parents)
+        return fail(h, NICNES_ERR_INVALID, "sensitivity slot out of range (-1: the shared vector)");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    if (slot < 0) {                    // one vector for every parent: the kernels read it with row stride 0
+        if (!es->svec) {
+            HIPC(h, hipDeviceSynchronize());
+            if (int rc = dalloc(h, &es->svec, (size_t)es->Dp)) return rc;
+            HIPC(h, nicnes_launch_es_sens_pad(es->svec, 1, es->Dp, h->D, s));
+        }
+        HIPC(h, hipMemcpyAsync(es->svec, vec_dev, (size_t)h->D * sizeof(float), hipMemcpyDeviceToDevice, s));
+        es->sens_shared = true;
+        return NICNES_OK;
+    }
+    if (int rc = es_sens_table(h, es, s)) return rc;
+    HIPC(h, hipMemcpyAsync(es->stab + (size_t)slot * (size_t)es->Dp, vec_dev, (size_t)h->D * sizeof(float),
+                           hipMemcpyDeviceToDevice, s));
+    es->sens_shared = false;
+    es->sens_valid[(size_t)slot] = 1;
+    return NICNES_OK;
+}
+
+int nicnes_get_sensitivity_es(nicnes_handle* h, int32_t slot, float* out_dev, void* stream) {
+    ES_STATE(h);
+    if (!out_dev || slot < 0 || slot >= es->max_parents) return fail(h, NICNES_ERR_INVALID, "sensitivity slot out of range");
+    const float* row = nullptr;
+    if (es->sens_shared)
+        row = es->svec;
+    else if (es->stab && es->sens_valid[(size_t)slot])
+        row = es->stab + (size_t)slot * (size_t)es->Dp;
+    if (!row) return fail(h, NICNES_ERR_INVALID, "the slot has no valid sensitivity");
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipMemcpyAsync(out_dev, row, (size_t)h->D * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return NICNES_OK;
 }
 
@@ -2744,6 +2851,8 @@ static EsMaterialise es_mat_args(const nicnes_handle* h, const nicnes_es* es, ui
     a.parents = es->ptab[es->cur];
     a.mean_abs = es->pmean[es->cur];
     a.elites = es->etab;
+    a.sens = es->sens_shared ? es->svec : es->stab;
+    a.sens_stride = es->sens_shared ? 0 : es->Dp;
     a.stride = es->Dp;
     a.dim = h->D;
     a.seed = h->cfg.noise_seed;
@@ -2760,6 +2869,7 @@ int nicnes_es_offspring(nicnes_handle* h, uint64_t generation, int32_t pair, int
     if (!theta32_out || pair < 0 || (sign != 0 && sign != 1)) return NICNES_ERR_INVALID;
     if (parent < 0 || parent >= es->n_parents) return fail(h, NICNES_ERR_INVALID, "parent outside [0, parent count)");
     if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
+    if (int rc = es_sens_ready(h, es, &parent, 1)) return rc;
     HIPC(h, hipSetDevice(h->device));
     EsMaterialise a = es_mat_args(h, es, generation, sigma);
     a.out = theta32_out;
@@ -2791,6 +2901,8 @@ int nicnes_es_advance(nicnes_handle* h, uint64_t generation, float sigma, const 
         n_front + n_keep > es->max_parents)
         return fail(h, NICNES_ERR_INVALID, "n_keep / n_front: out of range or beyond max_parents");
     if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
+    // (every pair's parent: which of them the survivors name is known only on the device)
+    if (int rc = es_sens_ready(h, es, parent_of_host, n_pairs)) return rc;
     hipStream_t s = (hipStream_t)stream;
     HIPC(h, hipSetDevice(h->device));
     if (int rc = es_stage_i32(h, parent_of_host, n_pairs, es->n_parents, es->parent_of, s, "parent_of")) return rc;
@@ -2806,6 +2918,7 @@ int nicnes_es_advance(nicnes_handle* h, uint64_t generation, float sigma, const 
                                           es->pzero[nxt], s));
     es->cur = nxt;
     es->n_parents = rows;
+    std::fill(es->sens_valid.begin(), es->sens_valid.end(), 0);   // the rows were the old table's (a shared vector stays)
     return NICNES_OK;
 }
 
@@ -2927,6 +3040,7 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
     if (es->n_parents < 1) return fail(h, NICNES_ERR_INVALID, "nicnes_es_set_parent_count first");
     int coop_S = 0;                    // 0: the fused path; 2 or 4: the coop path (nicnes_set_decode_es)
     if (int rc = es_decode_choice(h, h->B, count, &coop_S)) return rc;
+    if (int rc = es_sens_ready(h, es, parent_of_host, count)) return rc;
     hipStream_t s = (hipStream_t)stream;
     HIPC(h, hipSetDevice(h->device));
     const int32_t* mb = nullptr;
@@ -2936,10 +3050,15 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
                                       (uint64_t)h->D, h->nidx, s));
     DecodeParams p = decode_base(h);
     p.theta = es->ptab[es->cur];       // (every *_es kernel sets its workgroup's base from ParentArgs)
-    if (es->mode) {                    // proportional: the pairs' delta' rows
+    if (es->mode) {                    // proportional or divide: the pairs' delta' rows
         if (int rc = ensure_delta_rows(h, &es->dbuf, &es->didx, es->Dp, s)) return rc;
-        HIPC(h, nicnes_launch_es_mutate(h->noise, h->nidx, count, es->ptab[es->cur], es->parent_of, es->pmean[es->cur],
-                                        es->Dp, h->D, sigma, es->dbuf, s));
+        if (es->mode == NICNES_MUTATION_DIVIDE)
+            HIPC(h, nicnes_launch_es_mutate_divide(h->noise, h->nidx, count, es->sens_shared ? es->svec : es->stab,
+                                                   es->parent_of, es->sens_shared ? 0 : es->Dp, es->Dp, h->D, sigma,
+                                                   es->dbuf, s));
+        else
+            HIPC(h, nicnes_launch_es_mutate(h->noise, h->nidx, count, es->ptab[es->cur], es->parent_of, es->pmean[es->cur],
+                                            es->Dp, h->D, sigma, es->dbuf, s));
         p.noise = es->dbuf;
         p.noise_idx = es->didx;
     } else {                           // plain: the sigma-scaled table

@@ -56,6 +56,13 @@ extern "C" hipError_t nicnes_launch_scale(const float* in, float* out, uint64_t 
 extern "C" hipError_t nicnes_launch_es_mutate(const float* noise, const uint64_t* idx, int count, const float* parents,
                                               const int32_t* parent_of, const float* mean_abs, int64_t stride,
                                               int64_t dim, float sigma, float* out, hipStream_t s);
+// delta' rows of `count` pairs divided by their parents' sensitivity rows (SM-G-SUM, SM-VECTOR): row k reads
+// sens + parent_of[k] * sens_stride (sens_stride 0: one shared vector); out [count, stride]
+extern "C" hipError_t nicnes_launch_es_mutate_divide(const float* noise, const uint64_t* idx, int count, const float* sens,
+                                                     const int32_t* parent_of, int64_t sens_stride, int64_t stride,
+                                                     int64_t dim, float sigma, float* out, hipStream_t s);
+// 1.0 over the pad columns [dim, stride) of `rows` rows of a sensitivity table
+extern "C" hipError_t nicnes_launch_es_sens_pad(float* table, int rows, int64_t stride, int64_t dim, hipStream_t s);
 // mean|theta| (fp32 of an fp64 sum in a fixed order) and the zero count of `rows` table rows; part_sum / part_zero:
 // nicnes_es_stats_scratch(rows) entries each
 extern "C" size_t nicnes_es_stats_scratch(int rows);
@@ -71,6 +78,8 @@ struct EsMaterialise {
     const float* parents;        // current table
     const float* mean_abs;       // its rows' mean|theta|
     const float* elites;
+    const float* sens;           // mode 1: the parents' sensitivity rows, row p at sens + p * sens_stride
+    int64_t sens_stride;         // ... 0 for one shared vector
     const int32_t* parent_of;    // [pairs]
     const int32_t* order;        // [n_keep] offspring ids, or NULL
     float* out;                  // the other table (or one row)

@@ -498,9 +498,12 @@ extern "C" hipError_t nicnes_launch_scale(const float* in, float* out, uint64_t 
 
 // a_p[j] of SM-PROPORTIONAL with the parent as param_vector (nets.py:107-111): |theta_p[j]|, or mean|theta_p| at an
 // exact zero (either sign); delta'[j] = fp32(fp32(sigma z) * a)
-__device__ __forceinline__ float es_delta(float z, float sigma, float th, float mean_abs, int mode) {
+// mode 1 (SM-G-SUM, SM-VECTOR): delta'[j] = fp32(fp32(sigma z) / s_p[j]), IEEE division (mutate1's mode 1); s is read
+// by that mode only
+__device__ __forceinline__ float es_delta(float z, float sigma, float th, float mean_abs, int mode, float s = 1.f) {
     const float d = sigma * z;
     if (mode == 0) return d;
+    if (mode == 1) return d / s;
     const float a = th == 0.f ? mean_abs : __builtin_fabsf(th);
     return d * a;
 }
@@ -538,6 +541,56 @@ extern "C" hipError_t nicnes_launch_es_mutate(const float* noise, const uint64_t
     if (count <= 0) return hipSuccess;
     hipLaunchKernelGGL(nicnes_es_mutate_kernel, dim3(512, count), dim3(256), 0, s, noise, idx, parents, parent_of,
                        mean_abs, stride, dim, sigma, out);
+    return hipGetLastError();
+}
+
+// The DIVIDE form (SM-G-SUM, SM-VECTOR): out row k = fp32(sigma z) / s_p over the sensitivity row of the pair's parent,
+// sens + parent_of[k] * sens_stride (sens_stride = 0: one vector shared by every parent). The grid and the float4 path
+// of the kernel above; the parent's theta is not read.
+__global__ __launch_bounds__(256) void nicnes_es_mutate_divide_kernel(const float* __restrict__ noise,
+                                                                      const uint64_t* __restrict__ idx,
+                                                                      const float* __restrict__ sens,
+                                                                      const int32_t* __restrict__ parent_of,
+                                                                      int64_t sens_stride, int64_t stride, int64_t dim,
+                                                                      float sigma, float* __restrict__ out) {
+    const int k = blockIdx.y;
+    const float* z = noise + idx[k];
+    const float* sv = sens + (int64_t)parent_of[k] * sens_stride;
+    float* o = out + (int64_t)k * stride;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = dim / 4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += step) {
+        f32x4 zv, r;
+        __builtin_memcpy(&zv, z + 4 * i, 16);               // slice starts are multiples of 64 floats
+        const f32x4 s4 = reinterpret_cast<const f32x4*>(sv)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = es_delta(zv[e], sigma, 0.f, 0.f, 1, s4[e]);
+        __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(o) + i);
+    }
+    for (int64_t j = 4 * n4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < dim; j += step)
+        o[j] = es_delta(z[j], sigma, 0.f, 0.f, 1, sv[j]);
+}
+
+extern "C" hipError_t nicnes_launch_es_mutate_divide(const float* noise, const uint64_t* idx, int count, const float* sens,
+                                                     const int32_t* parent_of, int64_t sens_stride, int64_t stride,
+                                                     int64_t dim, float sigma, float* out, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(nicnes_es_mutate_divide_kernel, dim3(512, count), dim3(256), 0, s, noise, idx, sens, parent_of,
+                       sens_stride, stride, dim, sigma, out);
+    return hipGetLastError();
+}
+
+// 1.0 over the pad columns [dim, stride) of `rows` sensitivity rows (written once, when the table is allocated)
+__global__ void nicnes_es_sens_pad_kernel(float* table, int rows, int64_t stride, int64_t dim) {
+    const int64_t pad = stride - dim, i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int64_t)rows * pad) table[(i / pad) * stride + dim + i % pad] = 1.f;
+}
+
+extern "C" hipError_t nicnes_launch_es_sens_pad(float* table, int rows, int64_t stride, int64_t dim, hipStream_t s) {
+    const int64_t n = (int64_t)rows * (stride - dim);
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(nicnes_es_sens_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, table, rows, stride,
+                       dim);
     return hipGetLastError();
 }
 
@@ -664,6 +717,14 @@ __global__ __launch_bounds__(256) void nicnes_es_materialise_kernel(EsMaterialis
     }
     const float* z = a.noise + nn_noise_index(a.seed, a.generation, (uint64_t)pair, a.table_len, (uint64_t)a.dim);
     const float* th = a.parents + (int64_t)pi * a.stride;
+    if (a.mode == 1) {                 // the parent's sensitivity row (sens_stride = 0: the shared vector)
+        const float* sv = a.sens + (int64_t)pi * a.sens_stride;
+        for (int64_t j = j0; j < a.dim; j += step) {
+            const float t = th[j], d = es_delta(z[j], a.sigma, t, 0.f, 1, sv[j]);
+            o[j] = sign ? t - d : t + d;
+        }
+        return;
+    }
     const float mean = a.mode ? a.mean_abs[pi] : 0.f;
     for (int64_t j = j0; j < a.dim; j += step) {
         const float t = th[j], d = es_delta(z[j], a.sigma, t, mean, a.mode);

@@ -32,6 +32,7 @@ EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_create', 'nicne
            'nicnes_es_set_parent_count', 'nicnes_es_get_row', 'nicnes_es_row_stats', 'nicnes_es_evaluate',
            'nicnes_es_offspring', 'nicnes_es_select', 'nicnes_es_advance', 'nicnes_es_set_elite',
            'nicnes_es_load_theta', 'nicnes_set_decode_es', 'nicnes_decode_path_es', 'nicnes_allgather_fitness_es',
+           'nicnes_sensitivity_es', 'nicnes_set_sensitivity_es', 'nicnes_get_sensitivity_es', 'nicnes_set_mutation_divide_es',
            'nicnes_trainset_create', 'nicnes_trainset_write_fc', 'nicnes_trainset_destroy', 'nicnes_draw_batches', 'nicnes_test_batch_state']
 
 
@@ -134,6 +135,10 @@ def lib(path=None):
         'nicnes_es_create': (c.c_int, [vp, i32, i32]),
         'nicnes_es_free': (c.c_int, [vp]),
         'nicnes_es_set_mutation': (c.c_int, [vp, i32]),
+        'nicnes_set_mutation_divide_es': (c.c_int, [vp]),
+        'nicnes_sensitivity_es': (c.c_int, [vp, vp, i32, i32, f32, vp]),
+        'nicnes_set_sensitivity_es': (c.c_int, [vp, i32, vp, vp]),
+        'nicnes_get_sensitivity_es': (c.c_int, [vp, i32, vp, vp]),
         'nicnes_es_set_parent': (c.c_int, [vp, i32, vp, vp]),
         'nicnes_es_set_parent_count': (c.c_int, [vp, i32]),
         'nicnes_es_get_row': (c.c_int, [vp, i32, i32, vp, vp]),

@@ -587,9 +587,44 @@ class Engine:
         check(self.L.nicnes_es_free(self.h), self.h, 'es_free')
 
     def es_set_mutation(self, mode='plain'):
-        """'plain' or 'scale' (SM-PROPORTIONAL over each pair's own parent); anything else is not supported."""
+        """'plain' or 'scale' (SM-PROPORTIONAL over each pair's own parent); anything else is not supported ('divide',
+        which needs the parents' sensitivities, is es_set_mutation_divide)."""
         code = self.MUTATION_MODES[mode] if isinstance(mode, str) else int(mode)
         check(self.L.nicnes_es_set_mutation(self.h, code), self.h, 'es_set_mutation')
+
+    def es_set_mutation_divide(self):
+        """SM-G-SUM / SM-VECTOR: each pair's noise over its own parent's sensitivity (es_sensitivity, es_set_sensitivity).
+        es_evaluate, es_offspring and es_advance then raise, before anything is enqueued, when a parent they name has
+        no valid sensitivity. es_set_mutation('plain' / 'scale') leaves the mode."""
+        check(self.L.nicnes_set_mutation_divide_es(self.h), self.h, 'es_set_mutation_divide')
+
+    def es_sensitivity(self, slots, rows, underflow):
+        """The SM-G-SUM sensitivity (sum_sensitivity's kernels, clamp included) of each parent slot named, on the first
+        `rows` images of the batch held, into the handle's sensitivity table: one pass per slot, in order, on the
+        current stream. The rows stay valid until es_set_parent (that slot) or es_advance (all of them)."""
+        sl = self._host_i32(slots, len(slots), 'slots')
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_sensitivity_es(self.h, sl.ctypes.data_as(ctypes.c_void_p), int(sl.size), int(rows),
+                                               ctypes.c_float(underflow), self._stream()), self.h, 'es_sensitivity')
+
+    def es_set_sensitivity(self, vec, slot=None):
+        """slot None: `vec` [D] is the one sensitivity every parent shares (SM-VECTOR; it stays valid over advances).
+        slot >= 0: that parent's row (tests, resuming)."""
+        t = self._dev(vec, torch.float32)
+        if t.numel() != self.D:
+            raise ValueError('a sensitivity needs D entries')
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_set_sensitivity_es(self.h, -1 if slot is None else int(slot), _ptr(t), self._stream()),
+                  self.h, 'es_set_sensitivity')
+            torch.cuda.current_stream().synchronize()    # t stays alive until the copy has run
+
+    def es_sensitivity_row(self, slot):
+        """The sensitivity the divide mutation uses for parent `slot` (its row, or the shared vector): fp32 [D], GPU."""
+        out = torch.empty(self.D, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_get_sensitivity_es(self.h, int(slot), _ptr(out), self._stream()), self.h,
+                  'es_get_sensitivity')
+        return out
 
     def es_set_parent(self, slot, theta):
         t = self._dev(theta, torch.float32)

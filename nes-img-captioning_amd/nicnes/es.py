@@ -19,6 +19,8 @@ Where the engine departs from the reference (DESIGN.md, section "nic_es"):
 * Over several ranks (EngineESMaster(rank=, world_size=)) every rank evaluates its own es_shard of the pairs, the
   fitness is gathered, and selection, podium, schedule and the advance run replicated on every rank: the parent and
   elite tables stay identical with no theta ever sent (the reference's workers write every offspring to a shared disk).
+* SM-G-SUM: the sensitivity belongs to the parent, so a generation computes one vector per distinct parent drawn
+  (Engine.es_sensitivity), replicated on every rank, before the evaluate; SM-VECTOR shares one vector among all parents.
 * From zero, population_size host-initialised parents are perturbed; the reference makes generation 1's offspring
   fresh random models (ESIteration.init_from_zero keeps the parents None).
 """
@@ -83,9 +85,15 @@ class ESExperimentSpec:
             raise NotSupported('fitness %r: nic_es on the engine implements %s' % (po.fitness, ', '.join(GREEDY_FITNESS)))
         if po.vbn or mo.vbn_e or mo.layer_n:
             raise NotSupported('virtual batch norm / layer norm are not implemented by the engine')
-        if self.mutation not in ('', 'SM-PROPORTIONAL'):
-            raise NotSupported('safe_mutations %r: nic_es on the engine implements plain and SM-PROPORTIONAL'
-                               % self.mutation)
+        if self.mutation == 'SM-G-ABS':
+            raise NotSupported("SM-G-ABS: the reference's _calc_abs_sensitivity raises AttributeError "
+                               "(self.nb_params on Sensitivity, safe_mutations.py:125)")
+        if self.mutation not in ('', 'SM-PROPORTIONAL', 'SM-G-SUM', 'SM-VECTOR'):
+            raise NotSupported('safe_mutations %r (Mutation, src/algorithm/nets.py:16-21)' % self.mutation)
+        if self.mutation == 'SM-G-SUM' and not self.underflow > 0:
+            raise NotSupported('SM-G-SUM needs safe_mutation_underflow > 0 (the reference divides by it)')
+        if self.mutation == 'SM-VECTOR' and not mo.safe_mutation_vector:
+            raise NotSupported('SM-VECTOR needs model_options.safe_mutation_vector')
         if self.nb_offspring < 2 or self.nb_offspring % 2:
             raise NotSupported('nb_offspring %d: the engine evaluates antithetic pairs, so it must be even'
                                % self.nb_offspring)
@@ -107,6 +115,11 @@ class ESExperimentSpec:
     @property
     def mutation(self):
         return self.model_options.safe_mutations or ''
+
+    @property
+    def underflow(self):
+        """model_options.safe_mutation_underflow: the clamp of SM-G-SUM's sensitivity and of SM-VECTOR's file."""
+        return float(self.model_options.safe_mutation_underflow or 0.0)
 
     @property
     def n_pairs(self):
@@ -274,7 +287,13 @@ class EngineESMaster:
         if spec.n_pairs > engine.cfg.max_members:
             raise ValueError('the engine needs max_members >= nb_offspring / 2 = %d' % spec.n_pairs)
         engine.es_create(max(spec.population_size, 1), max(spec.num_elites, 1))
-        engine.es_set_mutation('scale' if spec.mutation == 'SM-PROPORTIONAL' else 'plain')
+        if spec.mutation in ('SM-G-SUM', 'SM-VECTOR'):
+            engine.es_set_mutation_divide()
+        else:
+            engine.es_set_mutation('scale' if spec.mutation == 'SM-PROPORTIONAL' else 'plain')
+        if spec.mutation == 'SM-VECTOR':          # one file, one vector for every parent of every generation
+            from .mutations import load_vector_file
+            engine.es_set_sensitivity(load_vector_file(spec.model_options.safe_mutation_vector, spec.underflow))
         engine.set_fitness_mode(spec.fitness)
         parents = self._initial_parents(thetas, from_single)
         engine.es_set_parents(parents)
@@ -384,6 +403,14 @@ class EngineESMaster:
             e.set_batch(fc, gts)
         parent_of = self.parents_of(g)
         begin, count = self.shard
+        if spec.mutation == 'SM-G-SUM':
+            # One sensitivity per distinct parent of the WHOLE generation, on every rank (the reference caches it per
+            # (task_id, parent_id), safe_mutations.py:34-52): the advance re-forms survivors of pairs other ranks
+            # decoded. Rows: the batch's unique images, the first orig_batch_size of them (Mutator.prepare's rule).
+            rows = int(e.B)
+            if rows > spec.batch_size > 0:
+                rows = spec.batch_size
+            e.es_sensitivity(sorted(set(int(p) for p in parent_of)), rows, spec.underflow)
         fit = self._gather_fitness(e.es_evaluate(g, begin, count, sigma, parent_of[begin:begin + count]))   # 1
         n_keep = spec.population_size - spec.num_elites
         order = e.es_select(fit, n_keep)                      # 4, enqueued behind the evaluate: no host sync between
