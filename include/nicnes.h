@@ -34,8 +34,16 @@ typedef struct nicnes_handle nicnes_handle;
  * src/captioning/experiment.py:27-30 vocab injection, src/algorithm/tools/utils.py:14-20 Config). */
 typedef struct nicnes_config {
     int32_t vocab_size;           /* V; logits are V + 1 wide (src/captioning/nets.py:151-152) */
-    int32_t input_encoding_size;  /* E (must be 128) */
-    int32_t rnn_size;             /* R (must be 128) */
+    int32_t input_encoding_size;  /* E: 128, 256, 384 or 512 */
+    int32_t rnn_size;             /* R: 128, 256, 384 or 512, independently of E. A model with E or R above 128 is
+                                   * "wide": every greedy decode (nicnes_evaluate*, nicnes_evaluate_theta,
+                                   * nicnes_split_decode / _evaluate, with the materialised mutations) runs on the wide
+                                   * path (nicnes_decode_path 3: 128-row slabs, one launch, one stream, the exact
+                                   * exp-sum); the sampled fitness modes, nicnes_sum_sensitivity, nicnes_es_create (all
+                                   * of nic_es), the beam decode, nicnes_test_logit_chain / _certify_items, a forced
+                                   * split shape (nicnes_set_decode_split with S > 1 or G = 2) and more than one decode
+                                   * stream return NICNES_ERR_UNSUPPORTED there. Test hook NICNES_DECODE_WIDE=1 (read
+                                   * at create): E = R = 128 takes the wide path too */
     int32_t fc_feat_size;         /* F (multiple of 128) */
     int32_t seq_length;           /* 16 (src/captioning/nets.py:147) */
     int32_t max_batch;            /* max unique images per batch (config.batch_size) */
@@ -396,7 +404,9 @@ int nicnes_decode_phase_times(nicnes_handle* h, float* out8_host);
  * (src/algorithm/nic_nes/nic_nes_worker.py:142-154); the engine spreads a member over S workgroups
  * when members x slabs cannot fill the GPU. S = 0 / G = 0 pick automatically (S from the CU count,
  * G = 2 -- 64-row slabs -- when B pads to fewer rows that way, e.g. mscoco_nes.json batch_size 64).
- * G = 4 with S = 1 is the fused path (one launch for every step). Tokens do not depend on the shape. */
+ * G = 4 with S = 1 is the fused path (one launch for every step). Tokens do not depend on the shape.
+ * On a wide handle (nicnes_decode_path 3) the shape is always G = 4, S = 1: S = 0 or 1 with G = 0 or 4 is accepted
+ * and changes nothing, S > 1 or G = 2 returns NICNES_ERR_UNSUPPORTED. */
 int nicnes_set_decode_split(nicnes_handle* h, int32_t S, int32_t G);
 /* the shape an evaluate of `count` members of a B-image batch would use: [0] G, [1] slabs, [2] S */
 int nicnes_decode_shape(nicnes_handle* h, int32_t B, int32_t count, int32_t* out3_host);
@@ -405,7 +415,8 @@ int nicnes_decode_shape(nicnes_handle* h, int32_t B, int32_t count, int32_t* out
  * part's launches fill the CUs the others' launch gaps leave idle. n = 0 picks automatically (2 on the
  * split path, 1 on the fused path), 1..4 forces; env NICNES_DECODE_STREAMS sets the initial value. A
  * multi-stream decode records no per-launch events (nicnes_decode_phase_times reports zeros).
- * Tokens do not depend on n. */
+ * Tokens do not depend on n. A wide handle decodes on one stream: n = 0 and 1 are accepted, n > 1 returns
+ * NICNES_ERR_UNSUPPORTED. */
 int nicnes_set_decode_streams(nicnes_handle* h, int32_t n);
 /* Coop decode (not a reference interface): when the split shape has 128-row slabs, S = 2 or 4 and every
  * workgroup fits on the GPU at once (S x members x slabs <= the kernel's occupancy x CUs, from
@@ -414,7 +425,9 @@ int nicnes_set_decode_streams(nicnes_handle* h, int32_t n);
  * that cannot be resident at once; 0.4 % slower per iteration at P = 64) whose S workgroups per
  * member slab hand the partial greedy states and h' to each other (mode 1, the default; env
  * NICNES_DECODE_COOP=0/1 sets the initial value), instead of two launches per step (mode 0). Tokens do not
- * depend on it. A partner missing for 0.5 s is a decode fault (nicnes_stats). */
+ * depend on it. A partner missing for 0.5 s is a decode fault (nicnes_stats).
+ * On a wide handle (nicnes_decode_path 3) the call is accepted, because the worker and nic_es layers set it on every
+ * engine of a shared device, and has no effect: there is no coop launch at wide dims, whatever the mode. */
 int nicnes_set_decode_coop(nicnes_handle* h, int32_t mode);
 
 /* SM-G-SUM sensitivity of the current theta on the first `rows` images of the batch held (batch 0):
@@ -426,7 +439,9 @@ int nicnes_set_decode_coop(nicnes_handle* h, int32_t mode);
  * with the reference's to fp32 rounding (a stated tolerance), not bit for bit. Asynchronous on stream. */
 int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, float* out_dev, void* stream);
 /* the decode path an evaluate of `count` members of a B-image batch would take: 0 fused (one launch,
- * one workgroup per member slab), 1 split (two launches per step), 2 coop (the split shape in one launch) */
+ * one workgroup per member slab), 1 split (two launches per step), 2 coop (the split shape in one launch), 3 wide (a
+ * model with input_encoding_size or rnn_size above 128, or NICNES_DECODE_WIDE=1: one launch, one workgroup per member
+ * and 128-row slab, whatever B and count) */
 int nicnes_decode_path(nicnes_handle* h, int32_t B, int32_t count, int32_t* out_host);
 /* the log-sum-exp mode of the last greedy decode enqueued: 1 the pair-bounded lse (greedy-only decodes while the
  * engine's adaptive policy allows it), 0 the exact exp-sum (log-probs written, NICNES_BOUNDED_LSE=0, or the policy's
@@ -441,7 +456,9 @@ int nicnes_last_decode_lse(nicnes_handle* h, int32_t* bounded_host);
  * env NICNES_SCREEN_ROUNDS (1..64, default 2): the round budget R. A lane with more hits than one hit list holds (8 hit
  * weights, a crowded lane-stage weighs 4) certifies them in further rounds while it holds at most 8 R; above that its
  * step goes to the fp32 loop. R bounds the weight, not the number of rounds: packing weights of 4 into rounds of 8 can
- * take a lane one round more than R. 1: no round after the first. */
+ * take a lane one round more than R. 1: no round after the first.
+ * On a wide handle (nicnes_decode_path 3) the call returns NICNES_OK and is ignored: the wide decode never screens, its
+ * logit loop is fp32 with the exact exp-sum whatever the mode, and the screening counters of nicnes_stats stay 0. */
 int nicnes_set_decode_screen(nicnes_handle* h, int32_t mode);
 /* Step queue of the screened decode (not a reference interface: the reference decodes a member's caption in one
  * FCModel._sample call, src/captioning/nets.py:183-245, and has no dispatch of its own; DESIGN.md 5, "Step queue"): mode 1
@@ -450,7 +467,9 @@ int nicnes_set_decode_screen(nicnes_handle* h, int32_t mode);
  * with the CU whose member slabs sum longest; mode 0 one workgroup per member slab; mode 2 (the default) the queue when
  * the decode has more member slabs than workers. workers 0: the device's CU count. Tokens do not depend on it. env
  * NICNES_DECODE_QUEUE=0/1/2 and NICNES_DECODE_QUEUE_WORKERS=n set the initial values. A wait in the queue that lasts
- * 0.5 s is a decode fault (nicnes_stats). */
+ * 0.5 s is a decode fault (nicnes_stats).
+ * On a wide handle (nicnes_decode_path 3) the call returns NICNES_OK and is ignored: the wide decode has no step queue
+ * and always runs one workgroup per member and 128-row slab. */
 int nicnes_set_decode_queue(nicnes_handle* h, int32_t mode, int32_t workers);
 /* The rule behind it, without a handle (pure; for tests and tools): for a screened fused decode of members x slabs
  * member slabs on a device of n_cu CUs, out3_host = {1 when the queue kernel runs, its workgroups, the ring's slots (a

@@ -186,5 +186,13 @@ extern "C" hipError_t nicnes_launch_beam_decode(const DecodeParams* p, int32_t* 
 // [n_img, K, V1], scores and live flags [n_img, K]; out [n_img, K, 2] (row of the image, id), pre-filled with -1
 extern "C" hipError_t nicnes_launch_test_beam_select(const float* lp, const double* score, const int32_t* live, int n_img,
                                                      int K, int V1, int32_t* out, hipStream_t stream);
+// the wide greedy decode (decode_wide_kernels.hip): E = input_encoding_size, R = rnn_size, each in {128, 256, 384, 512};
+// one launch of member_count x nslabs workgroups (p->G == 4, p->S == 1, greedy, no MutHead), exact exp-sum; p->scratch
+// holds nicnes_wide_scratch_floats(member_count * nslabs, E, R) floats. evs / kinds / n_launch as nicnes_launch_decode
+// (one launch, kind DK_STEPS). nicnes_decode_wide_init: per device, once per handle (its dynamic LDS is above 64 KB).
+extern "C" hipError_t nicnes_decode_wide_init();
+extern "C" size_t nicnes_wide_scratch_floats(int64_t workgroups, int E, int R);
+extern "C" hipError_t nicnes_launch_decode_wide(const DecodeParams* p, int E, int R, int member_count, int nslabs,
+                                                hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch);
 // lane scratch for up to member_count members x row_waves 32-row waves of one sign
 extern "C" size_t nicnes_decode_scratch_floats(int member_count, int row_waves_per_member);

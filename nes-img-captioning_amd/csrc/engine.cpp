@@ -121,6 +121,8 @@ struct nicnes_handle {
     float* noise_sc = nullptr;        // fp32(sc_sigma * table): what the decode kernels read (no multiply per use)
     float sc_sigma = 0.f;
     bool sc_valid = false;
+    bool wide = false;                // E or R above 128 (or the test hook NICNES_DECODE_WIDE=1): every decode request goes
+                                      // to the wide launcher (decode_wide_kernels.hip): 128-row slabs, one stream
     int mut_mode = 0;                 // nicnes_set_mutation: 0 plain, 1 divide, 2 multiply
     bool mut_full = false;            // NICNES_MUT_FULL=1: materialise every parameter's delta' (no decode-formed head)
     float* mut_vec = nullptr;         // [D] sensitivity (mode 1) or |theta| scale (mode 2)
@@ -383,6 +385,12 @@ int dalloc(nicnes_handle* h, T** p, size_t n) {
 }
 
 void decode_shape(const nicnes_handle* h, int B, int count, int* G, int* nslabs, int* S) {
+    if (h->wide) {            // the wide path: one workgroup per (member, 128-row slab)
+        *G = 4;
+        *nslabs = nslabs_of(B, 4);
+        *S = 1;
+        return;
+    }
     *G = h->dec_G ? h->dec_G : auto_G(B);
     *nslabs = nslabs_of(B, *G);
     *S = h->dec_S ? h->dec_S : auto_split((int64_t)count * *nslabs, h->n_cu, *G);
@@ -409,6 +417,7 @@ bool coop_fits(const nicnes_handle* h, int G, int nslabs, int S, int count) {
 // the screened decode's buffers: a capture slot per workgroup of the largest fused decode and the members' norms. If
 // they cannot be had, screening is off for this engine (the fp32 loop decodes the same tokens).
 void ensure_screen(nicnes_handle* h) {
+    if (h->wide) h->screen_mode = 0;             // the wide path sums the exp exactly: no screening, no step queue
     if (!h->screen_mode || (h->screen_cap && h->screen_norm)) return;
     const int64_t wgs = (int64_t)h->cfg.max_members * nslabs_of(h->cfg.max_batch, 4);
     bool ok = hipMalloc((void**)&h->screen_cap, (size_t)wgs * SCREEN_CAP_WORDS(h->V1) * sizeof(uint32_t)) == hipSuccess;
@@ -476,7 +485,10 @@ int alloc_batch(nicnes_handle* h, int max_batch) {
     int rc = dalloc(h, &h->seq, MM * 2 * MB * T);
     if (!rc) rc = dalloc(h, &h->lp, MM * 2 * MB * T);
     if (!rc) rc = dalloc(h, &h->row_scores, MM * 2 * MB);
-    if (!rc) rc = dalloc(h, &h->dscratch, nicnes_decode_scratch_floats((int)MM, rw));
+    // (the wide path: its lane scratch is sized from (E, R), one workgroup per member and 128-row slab)
+    const size_t wide_fl = h->wide ? nicnes_wide_scratch_floats((int64_t)MM * nslabs_of((int)MB, 4),
+                                                                h->cfg.input_encoding_size, h->cfg.rnn_size) : 0;
+    if (!rc) rc = dalloc(h, &h->dscratch, std::max(nicnes_decode_scratch_floats((int)MM, rw), wide_fl));
     if (!rc) rc = dalloc(h, &h->coop_ctr, MM * (size_t)ns * COOP_CTR_STRIDE);
     if (!rc) rc = dalloc(h, &h->alive, 3 * (size_t)h->alive_stride);
     if (!rc) rc = dalloc(h, &h->part, (size_t)h->part_cap * PART_FLOATS);
@@ -519,7 +531,8 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
     if (!cfg || !out) return NICNES_ERR_INVALID;
     *out = nullptr;
     const int V1 = cfg->vocab_size + 1;
-    if (cfg->input_encoding_size != 128 || cfg->rnn_size != 128) return NICNES_ERR_UNSUPPORTED;
+    const auto width_ok = [](int w) { return w == 128 || w == 256 || w == 384 || w == 512; };
+    if (!width_ok(cfg->input_encoding_size) || !width_ok(cfg->rnn_size)) return NICNES_ERR_UNSUPPORTED;
     if (cfg->fc_feat_size <= 0 || cfg->fc_feat_size % 128 != 0) return NICNES_ERR_UNSUPPORTED;
     if (V1 % 4 != 0 || V1 < 8 || V1 > 16384) return NICNES_ERR_UNSUPPORTED;
     if (cfg->seq_length < 1 || cfg->seq_length > 16) return NICNES_ERR_UNSUPPORTED;
@@ -529,6 +542,11 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
     h->cfg = *cfg;
     h->device = device;
     h->V1 = V1;
+    h->wide = cfg->input_encoding_size > 128 || cfg->rnn_size > 128;
+    {   // test hook: the default widths down the wide path too (bit-comparable with the fused kernel)
+        const char* dw = getenv("NICNES_DECODE_WIDE");
+        if (dw && dw[0] == '1' && dw[1] == 0) h->wide = true;
+    }
     layout(cfg, h->off);
     h->D = h->off[9];
     if (h->D * 4 >= (int64_t)1 << 32) {
@@ -585,6 +603,7 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
             h->n_cu = ncu;
     }
     if (!rc && nicnes_decode_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_init");
+    if (!rc && nicnes_decode_wide_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_wide_init");
     if (!rc && (nicnes_decode_occupancy(&h->coop_occ, &h->sample_occ) != hipSuccess || h->coop_occ < 1 ||
                 h->sample_occ < 1))
         rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_occupancy");
@@ -1164,6 +1183,9 @@ int nicnes_set_fitness_mode(nicnes_handle* h, int32_t mode) {
     if (mode < NICNES_FITNESS_GREEDY || mode > NICNES_FITNESS_SC_LOSS)
         return fail(h, NICNES_ERR_UNSUPPORTED, "fitness mode: the engine implements greedy, greedy_{log,exp,lin,avg}prob, "
                                                "sample, self_critical and sc_loss");
+    if (h->wide && mode >= NICNES_FITNESS_SAMPLE)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): the sampled fitness "
+                                               "modes are not supported (greedy, greedy_*)");
     h->fitness_mode = mode;
     return NICNES_OK;
 }
@@ -1315,6 +1337,7 @@ static int lse_poll(nicnes_handle* h) {
 
 // the policy as it stands (nicnes_split_decode reads it without advancing it: tokens do not depend on the lse mode)
 static bool lse_bounded_now(const nicnes_handle* h) {
+    if (h->wide) return false;                    // the wide path: the exact exp-sum only
     return h->bounded_mode == 1 || (h->bounded_mode == 2 && h->exact_left == 0);
 }
 
@@ -1366,8 +1389,15 @@ static int launch_decode_parts(nicnes_handle* h, const DecodeParams& p, const Mu
     } while (0)
     // the coop launch needs all its workgroups resident: never split over streams. (nic_es decodes with S == 1 unless
     // coop, so the same rule gives it one stream unless nicnes_set_decode_streams asks for more)
-    const int nstr = p.coop ? 1 : std::min(count, h->dec_streams ? h->dec_streams : (p.S == 1 ? 1 : 2));
-    if (nstr > 1) {
+    const int nstr = p.coop || h->wide ? 1 : std::min(count, h->dec_streams ? h->dec_streams : (p.S == 1 ? 1 : 2));
+    if (h->wide) {
+        // the wide path: one launch on the caller's stream; no MutHead (the delta' rows are whole), no nic_es parents
+        if (pa || mh.mode || sa.cap || p.sample_u)
+            return -fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): greedy decode "
+                                                    "only");
+        HIPN(nicnes_launch_decode_wide(&p, h->cfg.input_encoding_size, h->cfg.rnn_size, count, nslabs, s,
+                                       timed ? h->dev : nullptr, h->dev_kind, n_ev));
+    } else if (nstr > 1) {
         // members split evenly over the caller's stream and nstr - 1 engine streams; the parts share
         // nothing but the fallback counter (an atomic). No per-launch events: the launches overlap
         if (!h->ev_fork) HIPN(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
@@ -1466,6 +1496,9 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
     if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
+    if (h->wide && sampled)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): the sampled fitness "
+                                               "modes are not supported (greedy, greedy_*)");
     hipStream_t s = (hipStream_t)stream;
     HIPC(h, hipSetDevice(h->device));
     // rollout rows: the images, or rpi copies of each in the sampled modes (the reference's seq_per_img rows);
@@ -1574,7 +1607,7 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
         // the members' delta' rows. On the fused greedy path only the parameters from off_log_w on (logit, i2h, h2h,
         // which every step re-reads) are materialised; the decode forms the image projection's and the embedding
         // rows' delta' itself from sigma z and the vector (DecodeParams::mut_head): 5.6 of the 11.5 MB per member
-        const bool head = !sampled && !p.coop && G == 4 && S == 1 && !h->mut_full;
+        const bool head = !sampled && !p.coop && G == 4 && S == 1 && !h->mut_full && !h->wide;
         const int64_t j0 = head ? h->off[3] : 0;
         HIPC(h, nicnes_launch_mutate(h->noise + j0, h->nidx, count, h->D - j0, sigma, h->mut_vec + j0, h->mut_mode,
                                      h->dbuf + j0, h->Dp, s));
@@ -1754,7 +1787,9 @@ static int split_grow(nicnes_handle* h, nicnes_split* sp, int n_pm, int64_t n_lw
         // a pseudo-member is one 128-row slab or two 64-row slabs: 8 row waves of lane scratch, <= 2 workgroups
         int rc = dalloc(h, &sp->seq, rows * T);
         if (!rc) rc = dalloc(h, &sp->lp, rows * T);
-        if (!rc) rc = dalloc(h, &sp->scratch, nicnes_decode_scratch_floats(n_pm, 8));
+        if (!rc) rc = dalloc(h, &sp->scratch, std::max(nicnes_decode_scratch_floats(n_pm, 8),
+                                                       h->wide ? nicnes_wide_scratch_floats(n_pm, h->cfg.input_encoding_size,
+                                                                                            h->cfg.rnn_size) : (size_t)0));
         if (!rc) rc = dalloc(h, &sp->alive, 3 * 2 * PM);
         if (!rc) rc = dalloc(h, &sp->coop_ctr, 2 * PM * COOP_CTR_STRIDE);
         if (!rc) rc = dalloc(h, &sp->zero_idx, PM);
@@ -1924,6 +1959,9 @@ static int split_decode_beam_impl(nicnes_handle* h, nicnes_split* sp, int32_t fi
                                   int32_t* seq_out, double* score_out, hipStream_t s, const int32_t** seq_dev) {
     if (!split_of(h, sp)) return fail(h, NICNES_ERR_INVALID, "not a split of this handle");
     if (beam < 1 || beam > 8) return fail(h, NICNES_ERR_INVALID, "beam out of [1, 8]");
+    if (h->wide)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): the beam decode is "
+                                               "not supported");
     if (first < 0 || count < 1 || (int64_t)first + count > sp->N)
         return fail(h, NICNES_ERR_INVALID, "range outside the split's images");
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
@@ -2016,6 +2054,9 @@ static int sens_of_theta(nicnes_handle* h, const float* theta, int32_t rows, flo
 
 int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, float* out, void* stream) {
     if (!h || !out || rows < 1) return NICNES_ERR_INVALID;
+    if (h->wide)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): the SM-G-SUM "
+                                               "sensitivity is not supported");
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
     if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
     if (rows > h->B) return fail(h, NICNES_ERR_INVALID, "rows beyond the batch held");
@@ -2336,6 +2377,9 @@ int nicnes_decode_phase_times(nicnes_handle* h, float* out8_host) {
 
 int nicnes_set_decode_streams(nicnes_handle* h, int32_t n) {
     if (!h || n < 0 || n > 4) return NICNES_ERR_INVALID;
+    if (h->wide && n > 1)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): the decode runs on "
+                                               "one stream, more are not supported");
     h->dec_streams = n;
     return NICNES_OK;
 }
@@ -2358,6 +2402,9 @@ int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member
     if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
     if (h->mut_mode) return fail(h, NICNES_ERR_UNSUPPORTED, "nicnes_test_logit_chain: plain mutations only");
+    if (h->wide)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): "
+                                               "nicnes_test_logit_chain takes a 128-wide h: not supported");
     hipStream_t s = (hipStream_t)stream;
     HIPC(h, hipSetDevice(h->device));
     if (int rc = ensure_noise_scaled(h, sigma, s)) return rc;
@@ -2384,6 +2431,9 @@ int nicnes_test_certify_items_owned(nicnes_handle* h, uint64_t iteration, int32_
     if (!h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
     if (h->mut_mode) return fail(h, NICNES_ERR_UNSUPPORTED, "nicnes_test_certify_items: plain mutations only");
+    if (h->wide)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): "
+                                               "nicnes_test_certify_items takes a 128-wide h: not supported");
     for (int32_t i = 0; i < n_items; ++i) {
         const int32_t row = items_host[2 * i], id = items_host[2 * i + 1];
         if (row < 0 || row >= 128) return fail(h, NICNES_ERR_INVALID, "nicnes_test_certify_items: row outside [0, 128)");
@@ -2454,12 +2504,15 @@ int nicnes_decode_path(nicnes_handle* h, int32_t B, int32_t count, int32_t* out_
     if (!h || !out_host || B < 1 || count < 1) return NICNES_ERR_INVALID;
     int G = 0, nslabs = 0, S = 0;
     decode_shape(h, B, count, &G, &nslabs, &S);
-    *out_host = S == 1 ? 0 : coop_fits(h, G, nslabs, S, count) ? 2 : 1;
+    *out_host = h->wide ? 3 : S == 1 ? 0 : coop_fits(h, G, nslabs, S, count) ? 2 : 1;
     return NICNES_OK;
 }
 
 int nicnes_set_decode_split(nicnes_handle* h, int32_t S, int32_t G) {
     if (!h || S < 0 || S > 64 || (G != 0 && G != 2 && G != 4)) return NICNES_ERR_INVALID;
+    if (h->wide && (S > 1 || G == 2))
+        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): one workgroup per "
+                                               "member and 128-row slab, a forced split shape is not supported");
     HIPC(h, hipSetDevice(h->device));
     if (S > 0) {
         const int ns = std::max(nslabs_of(h->cfg.max_batch, 2), nslabs_of(h->cfg.max_batch, 4));
@@ -2603,6 +2656,9 @@ int nicnes_es_free(nicnes_handle* h) {
 
 int nicnes_es_create(nicnes_handle* h, int32_t max_parents, int32_t max_elites) {
     if (!h || max_parents < 1 || max_elites < 1 || max_elites > max_parents) return NICNES_ERR_INVALID;
+    if (h->wide)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): nic_es is not "
+                                               "supported");
     if (h->es) return fail(h, NICNES_ERR_INVALID, "nicnes_es_create: the handle has an ES state (nicnes_es_free first)");
     HIPC(h, hipSetDevice(h->device));
     nicnes_es* es = new nicnes_es();

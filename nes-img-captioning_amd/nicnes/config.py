@@ -10,6 +10,8 @@ implements the mscoco_nes.json hot path only: net 'fc_caption', every Fitness va
 greedy_* criteria, and the sampled sample / self_critical / sc_loss), model_options.safe_mutations
 '' / SM-G-SUM / SM-VECTOR / SM-PROPORTIONAL (nicnes.mutations), no vbn / layer_n; anything else
 raises NotSupported (nicnes_create returns NICNES_ERR_UNSUPPORTED for unsupported model sizes).
+model_options.rnn_size / input_encoding_size may each be 128, 256, 384 or 512; above 128 (is_wide) the
+sampled fitness values and SM-G-SUM raise NotSupported, as the engine refuses them there.
 """
 import json
 from collections import namedtuple
@@ -43,6 +45,12 @@ FITNESS = GREEDY_FITNESS + SAMPLED_FITNESS          # every Fitness enum value (
 
 class NotSupported(ValueError):
     pass
+
+
+def is_wide(model_options):
+    """A model is wide when rnn_size or input_encoding_size is above 128 (0 / absent: the default 128). The engine
+    decodes wide models on its wide greedy path (widths 128, 256, 384, 512; nicnes_create refuses others)."""
+    return int(model_options.rnn_size or 128) > 128 or int(model_options.input_encoding_size or 128) > 128
 
 
 def load_experiment(path_or_dict):
@@ -94,6 +102,16 @@ class ExperimentSpec:
                                "(self.nb_params on Sensitivity, safe_mutations.py:125)")
         if m not in ('', 'SM-G-SUM', 'SM-VECTOR', 'SM-PROPORTIONAL'):
             raise NotSupported('safe_mutations %r (Mutation, src/algorithm/nets.py:16-21)' % m)
+        if is_wide(mo):
+            # what the engine refuses at wide dims (nicnes_set_fitness_mode, nicnes_sum_sensitivity) is refused here,
+            # never ignored
+            if self.fitness in SAMPLED_FITNESS:
+                raise NotSupported('fitness %r: models wider than 128 units (rnn_size %s, input_encoding_size %s) decode '
+                                   'greedily only (%s)' % (self.fitness, mo.rnn_size, mo.input_encoding_size,
+                                                           ', '.join(GREEDY_FITNESS)))
+            if m == 'SM-G-SUM':
+                raise NotSupported('SM-G-SUM: the sensitivity is not implemented for models wider than 128 units '
+                                   '(rnn_size %s, input_encoding_size %s)' % (mo.rnn_size, mo.input_encoding_size))
 
     # ------------------------------------------------------------------------------------
     @property

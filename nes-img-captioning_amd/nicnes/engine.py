@@ -564,10 +564,11 @@ class Engine:
         return out
 
     def decode_path(self, B=None, count=1):
-        """'fused', 'split' or 'coop': the decode path an evaluate of `count` members would take."""
+        """'fused', 'split', 'coop' or 'wide': the decode path an evaluate of `count` members would take ('wide': a model
+        with rnn_size or input_encoding_size above 128, whatever B and count)."""
         out = ctypes.c_int32()
         check(self.L.nicnes_decode_path(self.h, int(B or self.B), int(count), ctypes.byref(out)), self.h, 'decode_path')
-        return ('fused', 'split', 'coop')[out.value]
+        return ('fused', 'split', 'coop', 'wide')[out.value]
 
     def decode_shape(self, B=None, count=1):
         """(G, slabs, S) an evaluate of `count` members would use."""

@@ -31,7 +31,7 @@ from collections import namedtuple
 import numpy as np
 
 from .config import (Config, PolicyOptions, ModelOptions, NotSupported, GREEDY_FITNESS, load_experiment,
-                     _model_opt_fields)
+                     _model_opt_fields, is_wide)
 
 result_fields = ['worker_id', 'evaluated_model_id', 'fitness', 'evaluated_model', 'eval_return', 'mem_usage',
                  'evaluated_cand', 'evaluated_cand_id', 'score']
@@ -81,6 +81,10 @@ class ESExperimentSpec:
         po, mo = self.policy_options, self.model_options
         if po.net != 'fc_caption':
             raise NotSupported('net %r: the engine implements fc_caption' % po.net)
+        if is_wide(mo):
+            raise NotSupported('nic_es is not implemented for models wider than 128 units (rnn_size %s, '
+                               'input_encoding_size %s): nicnes_es_create refuses them'
+                               % (mo.rnn_size, mo.input_encoding_size))
         if self.fitness not in GREEDY_FITNESS:
             raise NotSupported('fitness %r: nic_es on the engine implements %s' % (po.fitness, ', '.join(GREEDY_FITNESS)))
         if po.vbn or mo.vbn_e or mo.layer_n:

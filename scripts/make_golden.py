@@ -10,6 +10,8 @@ Fixtures (all .npz, loadable with allow_pickle=False):
   decode_full_{xavier,wc}.npz     full fc_caption dims (V=9487, E=R=128, F=2048); theta and fc are
                                   regenerated from the stored seeds (oracle.make_theta / numpy PCG64),
                                   plus two table-perturbed members (theta+delta, theta-delta)
+  decode_wide.npz                 the same at (E, R) = (256, 256), (128, 384), (512, 128) with V = 67, F = 128
+                                  (theta and fc from seeds, two table-perturbed members each)
   perturb_semantics.npz           PolicyNet.evolve (src/algorithm/nets.py:83-119): new params ==
                                   fp32(theta + delta), and worker's theta - delta (nic_nes_worker.py:151)
   adam.npz                        Adam.update (src/algorithm/nic_nes/optimizers.py:15-22,78-83) driven
@@ -116,7 +118,8 @@ def ref_decode(model, fc):
     return seq.numpy().astype(np.int32), slp.numpy().astype(np.float32), margins
 
 
-def decode_fixture(name, d, theta_seed, gain, bias_std, fc_seed, B, store_theta, members=()):
+def decode_case(d, theta_seed, gain, bias_std, fc_seed, B, store_theta, members=(), noise_len=1 << 23):
+    """What decode_fixture stores, as a dict."""
     model = ref_model(d)
     theta = O.make_theta(d, theta_seed, gain, bias_std)
     fc = np.random.Generator(np.random.PCG64(fc_seed)).standard_normal((B, d.F)).astype(np.float32)
@@ -130,7 +133,7 @@ def decode_fixture(name, d, theta_seed, gain, bias_std, fc_seed, B, store_theta,
         out['fc'] = fc
     # table-perturbed members (theta +- fp32(sigma z)), the engine's noise contract
     if members:
-        T, tseed, nseed, it, sigma = 1 << 23, 123, 7, 3, 0.01
+        T, tseed, nseed, it, sigma = noise_len, 123, 7, 3, 0.01
         table = O.noise_table(T, tseed)
         out.update(noise_len=np.int64(T), table_seed=np.int64(tseed), noise_seed=np.int64(nseed),
                    iteration=np.int64(it), sigma=np.float64(sigma), members=np.array(members, np.int64))
@@ -144,8 +147,31 @@ def decode_fixture(name, d, theta_seed, gain, bias_std, fc_seed, B, store_theta,
                 pmar.append(m)
         out['member_seq'] = np.stack(pseq)       # [members*2, B, T] order (m0+, m0-, m1+, ...)
         out['member_margins'] = np.stack(pmar)
+    return out
+
+
+def decode_fixture(name, d, theta_seed, gain, bias_std, fc_seed, B, store_theta, members=()):
+    out = decode_case(d, theta_seed, gain, bias_std, fc_seed, B, store_theta, members)
     np.savez_compressed(os.path.join(OUT, name + '.npz'), **out)
-    print(name, 'seq[0]', seq[0], 'min margin', float(mar.min()))
+    print(name, 'seq[0]', out['seq'][0], 'min margin', float(out['margins'].min()))
+
+
+# (E, R) of decode_wide.npz: 2, 1 and 4 k windows of 128 in the i2h / img products, 2, 3 and 1 in the h2h / logit ones
+WIDE_CASES = (('e256_r256', 256, 256, 1301), ('e128_r384', 128, 384, 1302), ('e512_r128', 512, 128, 1303))
+
+
+def decode_wide_fixture():
+    """decode_wide.npz: FCModel._sample on models wider than 128 units, vocabulary 67 (V1 = 68) and F = 128; theta and
+    fc regenerated from their seeds (well-conditioned theta), theta itself and two table-perturbed members (both signs)
+    per case. Keys are '<case>/<key>' with decode_fixture's keys."""
+    out = {'cases': np.array([c[0] for c in WIDE_CASES])}
+    for name, E, R, fc_seed in WIDE_CASES:
+        d = O.Dims(vocab_size=67, E=E, R=R, F=128)
+        one = decode_case(d, 0, 4.0, 0.1, fc_seed, 16, False, members=(0, 1), noise_len=1 << 21)
+        out.update({'%s/%s' % (name, k): v for k, v in one.items()})
+        print('decode_wide', name, 'seq[0]', one['seq'][0], 'min margin', float(one['margins'].min()),
+              'min member margin', float(one['member_margins'].min()))
+    np.savez_compressed(os.path.join(OUT, 'decode_wide.npz'), **out)
 
 
 BENCH_MEMBERS = np.array(sorted(set(np.linspace(0, 511, 8).astype(np.int64).tolist())
@@ -526,6 +552,7 @@ def all_fixtures():
     decode_fixture('decode_full_xavier', full, 0, 1.0, 0.0, 1234, 16, False, members=(0, 1))
     decode_fixture('decode_full_wc', full, 0, 4.0, 0.1, 1234, 16, False, members=(0, 1))
     decode_sample_fixture()
+    decode_wide_fixture()
     perturb_fixture()
     adam_fixture()
     ranks_fixture()
