@@ -51,12 +51,28 @@ typedef struct nicnes_config {
     int32_t max_members;          /* max population members per nicnes_evaluate call */
     uint64_t noise_len;           /* entries of the shared Gaussian table */
     uint64_t noise_seed;          /* seed of the member -> table-offset rule */
+    int32_t layer_n;              /* model_options.layer_n: LSTMCore with nn.LayerNorm on i2h(x), h2h(h) (each over 5R) and
+                                   * on next_c (over R) in front of the tanh (src/captioning/nets.py:92-96,102-104,
+                                   * 126-127). At every supported width such a handle decodes on the layer-norm path
+                                   * (nicnes_decode_path 4): the wide path's shape and rules (128-row slabs, one launch,
+                                   * one stream, the exact exp-sum, materialised mutations) on a kernel whose cell forms the
+                                   * row statistics, and it ignores or refuses what a wide handle ignores or refuses
+                                   * (see rnn_size above). 0: no normalisation */
+    int32_t layer_n_affine;       /* model_options.layer_n_affine: the three LayerNorms carry weight and bias; theta
+                                   * then holds six more tensors behind the nine (nicnes_param_offsets_ln), perturbed,
+                                   * mutated and optimised like every other entry. Ignored without layer_n, as the
+                                   * reference ignores it */
 } nicnes_config;
 
 /* flat parameter count D for a config (src/algorithm/nets.py:146-148 count_parameters) */
 int64_t nicnes_param_count(const nicnes_config* cfg);
-/* offsets of the 9 tensors in the flat theta (registration order) + D at [9] */
+/* offsets of the 9 tensors in the flat theta (registration order) + D at [9] (with layer_n_affine D includes the six
+ * layer-norm tensors behind them, so [9] is then the end of theta and not of core.h2h.bias) */
 int nicnes_param_offsets(const nicnes_config* cfg, int64_t* out10_host);
+/* layer_n with layer_n_affine: offsets of core.i2h_ln.weight, .bias [5R], core.h2h_ln.weight, .bias [5R],
+ * core.c_ln.weight, .bias [R] (the reference's registration order: they follow core.h2h.bias) + D at [6].
+ * NICNES_ERR_INVALID on a config without both flags. */
+int nicnes_param_offsets_ln(const nicnes_config* cfg, int64_t* out7_host);
 
 int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out);
 int nicnes_destroy(nicnes_handle* h);
@@ -441,7 +457,7 @@ int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, floa
 /* the decode path an evaluate of `count` members of a B-image batch would take: 0 fused (one launch,
  * one workgroup per member slab), 1 split (two launches per step), 2 coop (the split shape in one launch), 3 wide (a
  * model with input_encoding_size or rnn_size above 128, or NICNES_DECODE_WIDE=1: one launch, one workgroup per member
- * and 128-row slab, whatever B and count) */
+ * and 128-row slab, whatever B and count), 4 ln (a layer_n model: the wide shape on the layer-norm kernel) */
 int nicnes_decode_path(nicnes_handle* h, int32_t B, int32_t count, int32_t* out_host);
 /* the log-sum-exp mode of the last greedy decode enqueued: 1 the pair-bounded lse (greedy-only decodes while the
  * engine's adaptive policy allows it), 0 the exact exp-sum (log-probs written, NICNES_BOUNDED_LSE=0, or the policy's
@@ -496,6 +512,13 @@ int nicnes_screen_reasons(nicnes_handle* h, int64_t* out16_host);
  * only. Asynchronous on stream. */
 int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member, float sigma, int32_t sign,
                             const float* h_rows_dev, float* out_mfma_dev, float* out_chain_dev, void* stream);
+/* Test entry (no reference counterpart), layer_n handles only: one LSTM cell of theta itself (no perturbation) on
+ * `rows` <= 128 given rows, x_dev [rows, input_encoding_size], h_dev and c_dev [rows, rnn_size] fp32 in unit order, by
+ * the device function the layer-norm decode runs its cells with (the rows are spread to one workgroup's lane scratch
+ * in the decode's layout, so no decode may run beside it); h_out_dev and c_out_dev [rows, rnn_size] receive h' and
+ * the un-normalised c'. Asynchronous on stream. */
+int nicnes_test_ln_cell(nicnes_handle* h, const float* x_dev, const float* h_dev, const float* c_dev, int32_t rows,
+                        float* h_out_dev, float* c_out_dev, void* stream);
 /* Test entry (no reference counterpart): given candidates through the screened decode's tile certify (DESIGN.md
  * 5). h_rows_dev [128, 128] fp32 (unit order) is laid out as the lane scratch of one decode workgroup's eight waves;
  * items_host [n_items, 2] int32 (HOST) holds (row in [0, 128), vocabulary id in [0, vocab_size]) pairs in any order,

@@ -138,6 +138,48 @@ NN_FN void nn_lstm_cell(float s_in, float s_forget, float s_out, float s_g1, flo
     *h_new = og * nn_tanhf(cn);
 }
 
+/*
+ * Layer norm of the N values of one batch row (nn.LayerNorm, src/captioning/nets.py:94-96: biased variance,
+ * eps = 1e-5). In the 32x32 accumulator layout the row's values sit in two lanes, each holding the units it produced
+ * (lane half hh owns unit u when ((u >> 2) & 1) == hh), and each lane sums its own values sequentially in ascending
+ * unit order. A statistic is then finished from the two lane sums:
+ *   mean = (sum_a + sum_b) / (float)N;   d = a - mean;   den = sqrtf((sumsq_a + sumsq_b) / (float)N + 1e-5f)
+ * where sumsq is the lane's sequential sum of d * d in the same order (two passes: never E[x^2] - mean^2), and
+ *   y = d / den,   with affine  y * gamma + beta  (a rounded product, then a rounded sum).
+ * Only +, -, *, / and sqrtf, each IEEE-rounded and unfused (-ffp-contract=off), so host and GPU agree bit for bit.
+ */
+#define NN_LN_EPS 1e-5f
+NN_FN float nn_ln_mean(float sum_a, float sum_b, int n) { return (sum_a + sum_b) / (float)n; }
+NN_FN float nn_ln_sq(float acc, float a, float mean) {   /* one term of the centred second pass */
+    const float d = a - mean;
+    const float dd = d * d;
+    return acc + dd;
+}
+NN_FN float nn_ln_den(float sumsq_a, float sumsq_b, int n) {
+    const float var = (sumsq_a + sumsq_b) / (float)n;
+    return sqrtf(var + NN_LN_EPS);
+}
+NN_FN float nn_ln_y(float a, float mean, float den) { return (a - mean) / den; }
+NN_FN float nn_ln_affine(float y, float gamma, float beta) {
+    const float t = y * gamma;
+    return t + beta;
+}
+
+/*
+ * LSTM cell element with layer_n (src/captioning/nets.py:102-130), in two halves around the row statistic of c':
+ *   c' = f*c + i*max(g1,g2)  from the gate sums s = LN(i2h(x)) + LN(h2h(h)); c' is the state, un-normalised;
+ *   h' = o * tanh(LN_c(c'))  with og = sigmoid(s_out) formed in the first half.
+ */
+NN_FN float nn_lstm_cell_ln_c(float s_in, float s_forget, float s_g1, float s_g2, float c) {
+    const float ig = nn_sigmoidf(s_in);
+    const float fg = nn_sigmoidf(s_forget);
+    const float g = s_g1 > s_g2 ? s_g1 : s_g2;
+    const float fc = fg * c;
+    const float igv = ig * g;
+    return fc + igv;
+}
+NN_FN float nn_lstm_cell_ln_h(float og, float c_normed) { return og * nn_tanhf(c_normed); }
+
 /* ---- noise-table index rule (the contract that replaces shipping 11 MB noise vectors,
  *      src/algorithm/nic_nes/nic_nes_worker.py:156-161) ---------------------------------- */
 NN_FN uint64_t nn_splitmix64(uint64_t x) {

@@ -194,5 +194,17 @@ extern "C" hipError_t nicnes_decode_wide_init();
 extern "C" size_t nicnes_wide_scratch_floats(int64_t workgroups, int E, int R);
 extern "C" hipError_t nicnes_launch_decode_wide(const DecodeParams* p, int E, int R, int member_count, int nslabs,
                                                 hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch);
+// the layer-norm greedy decode (decode_ln_kernels.hip; layer_n models at every supported width): the wide launch's shape
+// and rules with its own, larger lane scratch (nicnes_ln_scratch_floats). tail6: the theta offsets of the six affine
+// tensors (i2h_ln weight, bias, h2h_ln weight, bias, c_ln weight, bias), NULL without layer_n_affine.
+extern "C" hipError_t nicnes_decode_ln_init();
+extern "C" size_t nicnes_ln_scratch_floats(int64_t workgroups, int E, int R);
+extern "C" hipError_t nicnes_launch_decode_ln(const DecodeParams* p, int E, int R, const int64_t* tail6, int member_count,
+                                              int nslabs, hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch);
+// test entry (nicnes_test_ln_cell): one layer-norm cell of theta itself (p->noise: D zeros) on rows <= 128 given rows
+// xin [rows, E], hin [rows, R], cin [rows, R] by the decode's device function; p->scratch holds one workgroup's lane scratch
+extern "C" hipError_t nicnes_launch_test_ln_cell(const DecodeParams* p, int E, int R, const int64_t* tail6,
+                                                 const float* xin, const float* hin, const float* cin, int rows,
+                                                 float* hout, float* cout, hipStream_t stream);
 // lane scratch for up to member_count members x row_waves 32-row waves of one sign
 extern "C" size_t nicnes_decode_scratch_floats(int member_count, int row_waves_per_member);

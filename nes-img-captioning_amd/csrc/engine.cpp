@@ -123,6 +123,10 @@ struct nicnes_handle {
     bool sc_valid = false;
     bool wide = false;                // E or R above 128 (or the test hook NICNES_DECODE_WIDE=1): every decode request goes
                                       // to the wide launcher (decode_wide_kernels.hip): 128-row slabs, one stream
+    bool ln = false;                  // cfg.layer_n: a wide handle whose launcher is the layer-norm one
+                                      // (decode_ln_kernels.hip), at every width; ln_off: the six affine tensors' offsets
+    bool ln_affine = false;           // cfg.layer_n_affine (with layer_n): theta carries the six tensors at its tail
+    int64_t ln_off[6] = {0, 0, 0, 0, 0, 0};
     int mut_mode = 0;                 // nicnes_set_mutation: 0 plain, 1 divide, 2 multiply
     bool mut_full = false;            // NICNES_MUT_FULL=1: materialise every parameter's delta' (no decode-formed head)
     float* mut_vec = nullptr;         // [D] sensitivity (mode 1) or |theta| scale (mode 2)
@@ -293,6 +297,11 @@ struct nicnes_trainset {
 
 namespace {
 
+// how a refusal on the wide path names the handle's model
+std::string wide_what(const nicnes_handle* h) {
+    return h->ln ? "layer_n models: " : "wide models (rnn_size or input_encoding_size above 128): ";
+}
+
 int fail(nicnes_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg;
     return code;
@@ -319,6 +328,25 @@ void layout(const nicnes_config* c, int64_t* off) {
     off[7] = o; o += 5 * R * R;    // core.h2h.weight
     off[8] = o; o += 5 * R;        // core.h2h.bias
     off[9] = o;
+}
+
+// layer_n_affine (with layer_n; ignored without it, as the reference ignores it): six tensors appended behind the nine
+bool ln_affine_of(const nicnes_config* c) { return c->layer_n != 0 && c->layer_n_affine != 0; }
+
+// the six tail offsets + D; without affine off7[0..5] = off7[6] = the nine tensors' end
+void layout_ln(const nicnes_config* c, int64_t* off7) {
+    int64_t off[10];
+    layout(c, off);
+    const int64_t R = c->rnn_size;
+    const bool a = ln_affine_of(c);
+    int64_t o = off[9];
+    off7[0] = o; o += a ? 5 * R : 0;   // core.i2h_ln.weight
+    off7[1] = o; o += a ? 5 * R : 0;   // core.i2h_ln.bias
+    off7[2] = o; o += a ? 5 * R : 0;   // core.h2h_ln.weight
+    off7[3] = o; o += a ? 5 * R : 0;   // core.h2h_ln.bias
+    off7[4] = o; o += a ? R : 0;       // core.c_ln.weight
+    off7[5] = o; o += a ? R : 0;       // core.c_ln.bias
+    off7[6] = o;
 }
 
 // nicnes_allgather_fitness_es: the ranks' padded shares [world, pad, 2] compacted into pair order [n_pairs, 2]
@@ -467,6 +495,12 @@ int alloc_refs(nicnes_handle* h, int max_refs) {
 
 // Buffers sized by the batch: per-image n-gram tables, tokens / log-probs / row scores of a launch,
 // decode lane scratch, alive flags and partial states.
+// lane scratch of `workgroups` workgroups of the wide path's launcher (the layer-norm one on a layer_n handle)
+size_t wide_scratch_floats(const nicnes_handle* h, int64_t workgroups) {
+    const int E = h->cfg.input_encoding_size, R = h->cfg.rnn_size;
+    return h->ln ? nicnes_ln_scratch_floats(workgroups, E, R) : nicnes_wide_scratch_floats(workgroups, E, R);
+}
+
 int alloc_batch(nicnes_handle* h, int max_batch) {
     void* old[] = {h->seq, h->lp, h->row_scores, h->dscratch, h->alive, h->part};
     for (void* q : old)
@@ -486,8 +520,7 @@ int alloc_batch(nicnes_handle* h, int max_batch) {
     if (!rc) rc = dalloc(h, &h->lp, MM * 2 * MB * T);
     if (!rc) rc = dalloc(h, &h->row_scores, MM * 2 * MB);
     // (the wide path: its lane scratch is sized from (E, R), one workgroup per member and 128-row slab)
-    const size_t wide_fl = h->wide ? nicnes_wide_scratch_floats((int64_t)MM * nslabs_of((int)MB, 4),
-                                                                h->cfg.input_encoding_size, h->cfg.rnn_size) : 0;
+    const size_t wide_fl = h->wide ? wide_scratch_floats(h, (int64_t)MM * nslabs_of((int)MB, 4)) : 0;
     if (!rc) rc = dalloc(h, &h->dscratch, std::max(nicnes_decode_scratch_floats((int)MM, rw), wide_fl));
     if (!rc) rc = dalloc(h, &h->coop_ctr, MM * (size_t)ns * COOP_CTR_STRIDE);
     if (!rc) rc = dalloc(h, &h->alive, 3 * (size_t)h->alive_stride);
@@ -516,14 +549,21 @@ extern "C" {
 
 int64_t nicnes_param_count(const nicnes_config* cfg) {
     if (!cfg) return -1;
-    int64_t off[10];
-    layout(cfg, off);
-    return off[9];
+    int64_t off7[7];
+    layout_ln(cfg, off7);
+    return off7[6];
 }
 
 int nicnes_param_offsets(const nicnes_config* cfg, int64_t* out10_host) {
     if (!cfg || !out10_host) return NICNES_ERR_INVALID;
     layout(cfg, out10_host);
+    out10_host[9] = nicnes_param_count(cfg);     // D, the layer-norm tail included
+    return NICNES_OK;
+}
+
+int nicnes_param_offsets_ln(const nicnes_config* cfg, int64_t* out7_host) {
+    if (!cfg || !out7_host || !ln_affine_of(cfg)) return NICNES_ERR_INVALID;
+    layout_ln(cfg, out7_host);
     return NICNES_OK;
 }
 
@@ -547,7 +587,16 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
         const char* dw = getenv("NICNES_DECODE_WIDE");
         if (dw && dw[0] == '1' && dw[1] == 0) h->wide = true;
     }
+    h->ln = cfg->layer_n != 0;
+    h->ln_affine = ln_affine_of(cfg);
+    if (h->ln) h->wide = true;
     layout(cfg, h->off);
+    {
+        int64_t off7[7];
+        layout_ln(cfg, off7);
+        for (int i = 0; i < 6; ++i) h->ln_off[i] = off7[i];
+        h->off[9] = off7[6];
+    }
     h->D = h->off[9];
     if (h->D * 4 >= (int64_t)1 << 32) {
         delete h;
@@ -604,6 +653,7 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
     }
     if (!rc && nicnes_decode_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_init");
     if (!rc && nicnes_decode_wide_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_wide_init");
+    if (!rc && nicnes_decode_ln_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_ln_init");
     if (!rc && (nicnes_decode_occupancy(&h->coop_occ, &h->sample_occ) != hipSuccess || h->coop_occ < 1 ||
                 h->sample_occ < 1))
         rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_occupancy");
@@ -1184,7 +1234,7 @@ int nicnes_set_fitness_mode(nicnes_handle* h, int32_t mode) {
         return fail(h, NICNES_ERR_UNSUPPORTED, "fitness mode: the engine implements greedy, greedy_{log,exp,lin,avg}prob, "
                                                "sample, self_critical and sc_loss");
     if (h->wide && mode >= NICNES_FITNESS_SAMPLE)
-        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): the sampled fitness "
+        return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "the sampled fitness "
                                                "modes are not supported (greedy, greedy_*)");
     h->fitness_mode = mode;
     return NICNES_OK;
@@ -1393,10 +1443,15 @@ static int launch_decode_parts(nicnes_handle* h, const DecodeParams& p, const Mu
     if (h->wide) {
         // the wide path: one launch on the caller's stream; no MutHead (the delta' rows are whole), no nic_es parents
         if (pa || mh.mode || sa.cap || p.sample_u)
-            return -fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): greedy decode "
+            return -fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "greedy decode "
                                                     "only");
-        HIPN(nicnes_launch_decode_wide(&p, h->cfg.input_encoding_size, h->cfg.rnn_size, count, nslabs, s,
-                                       timed ? h->dev : nullptr, h->dev_kind, n_ev));
+        if (h->ln)
+            HIPN(nicnes_launch_decode_ln(&p, h->cfg.input_encoding_size, h->cfg.rnn_size,
+                                         h->ln_affine ? h->ln_off : nullptr, count, nslabs, s, timed ? h->dev : nullptr,
+                                         h->dev_kind, n_ev));
+        else
+            HIPN(nicnes_launch_decode_wide(&p, h->cfg.input_encoding_size, h->cfg.rnn_size, count, nslabs, s,
+                                           timed ? h->dev : nullptr, h->dev_kind, n_ev));
     } else if (nstr > 1) {
         // members split evenly over the caller's stream and nstr - 1 engine streams; the parts share
         // nothing but the fallback counter (an atomic). No per-launch events: the launches overlap
@@ -1497,7 +1552,7 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
     if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
     if (h->wide && sampled)
-        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): the sampled fitness "
+        return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "the sampled fitness "
                                                "modes are not supported (greedy, greedy_*)");
     hipStream_t s = (hipStream_t)stream;
     HIPC(h, hipSetDevice(h->device));
@@ -1788,8 +1843,7 @@ static int split_grow(nicnes_handle* h, nicnes_split* sp, int n_pm, int64_t n_lw
         int rc = dalloc(h, &sp->seq, rows * T);
         if (!rc) rc = dalloc(h, &sp->lp, rows * T);
         if (!rc) rc = dalloc(h, &sp->scratch, std::max(nicnes_decode_scratch_floats(n_pm, 8),
-                                                       h->wide ? nicnes_wide_scratch_floats(n_pm, h->cfg.input_encoding_size,
-                                                                                            h->cfg.rnn_size) : (size_t)0));
+                                                       h->wide ? wide_scratch_floats(h, n_pm) : (size_t)0));
         if (!rc) rc = dalloc(h, &sp->alive, 3 * 2 * PM);
         if (!rc) rc = dalloc(h, &sp->coop_ctr, 2 * PM * COOP_CTR_STRIDE);
         if (!rc) rc = dalloc(h, &sp->zero_idx, PM);
@@ -1960,7 +2014,7 @@ static int split_decode_beam_impl(nicnes_handle* h, nicnes_split* sp, int32_t fi
     if (!split_of(h, sp)) return fail(h, NICNES_ERR_INVALID, "not a split of this handle");
     if (beam < 1 || beam > 8) return fail(h, NICNES_ERR_INVALID, "beam out of [1, 8]");
     if (h->wide)
-        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): the beam decode is "
+        return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "the beam decode is "
                                                "not supported");
     if (first < 0 || count < 1 || (int64_t)first + count > sp->N)
         return fail(h, NICNES_ERR_INVALID, "range outside the split's images");
@@ -2055,7 +2109,7 @@ static int sens_of_theta(nicnes_handle* h, const float* theta, int32_t rows, flo
 int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, float* out, void* stream) {
     if (!h || !out || rows < 1) return NICNES_ERR_INVALID;
     if (h->wide)
-        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): the SM-G-SUM "
+        return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "the SM-G-SUM "
                                                "sensitivity is not supported");
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
     if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
@@ -2378,7 +2432,7 @@ int nicnes_decode_phase_times(nicnes_handle* h, float* out8_host) {
 int nicnes_set_decode_streams(nicnes_handle* h, int32_t n) {
     if (!h || n < 0 || n > 4) return NICNES_ERR_INVALID;
     if (h->wide && n > 1)
-        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): the decode runs on "
+        return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "the decode runs on "
                                                "one stream, more are not supported");
     h->dec_streams = n;
     return NICNES_OK;
@@ -2403,7 +2457,7 @@ int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
     if (h->mut_mode) return fail(h, NICNES_ERR_UNSUPPORTED, "nicnes_test_logit_chain: plain mutations only");
     if (h->wide)
-        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): "
+        return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) +
                                                "nicnes_test_logit_chain takes a 128-wide h: not supported");
     hipStream_t s = (hipStream_t)stream;
     HIPC(h, hipSetDevice(h->device));
@@ -2414,6 +2468,23 @@ int nicnes_test_logit_chain(nicnes_handle* h, uint64_t iteration, int32_t member
     p.scratch = h->dscratch;        // one wave's lane scratch holds the rows of h (no decode runs beside this)
     const uint64_t nidx = nn_noise_index(h->cfg.noise_seed, iteration, (uint64_t)member, h->cfg.noise_len, (uint64_t)h->D);
     HIPC(h, nicnes_launch_test_logit_chain(&p, nidx, sign, h_rows, out_mfma, out_chain, s));
+    return NICNES_OK;
+}
+
+int nicnes_test_ln_cell(nicnes_handle* h, const float* x_dev, const float* h_dev, const float* c_dev, int32_t rows,
+                        float* h_out, float* c_out, void* stream) {
+    if (!h || !x_dev || !h_dev || !c_dev || !h_out || !c_out || rows < 1 || rows > 128) return NICNES_ERR_INVALID;
+    if (!h->ln) return fail(h, NICNES_ERR_UNSUPPORTED, "nicnes_test_ln_cell: the handle has no layer_n");
+    if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    if (int rc = ensure_zero_noise(h)) return rc;
+    DecodeParams p = decode_base(h);
+    p.theta = h->theta32;
+    p.noise = h->zero_noise;        // theta itself
+    p.scratch = h->dscratch;        // one workgroup's lane scratch (no decode runs beside this)
+    HIPC(h, nicnes_launch_test_ln_cell(&p, h->cfg.input_encoding_size, h->cfg.rnn_size,
+                                       h->ln_affine ? h->ln_off : nullptr, x_dev, h_dev, c_dev, rows, h_out, c_out, s));
     return NICNES_OK;
 }
 
@@ -2432,7 +2503,7 @@ int nicnes_test_certify_items_owned(nicnes_handle* h, uint64_t iteration, int32_
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
     if (h->mut_mode) return fail(h, NICNES_ERR_UNSUPPORTED, "nicnes_test_certify_items: plain mutations only");
     if (h->wide)
-        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): "
+        return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) +
                                                "nicnes_test_certify_items takes a 128-wide h: not supported");
     for (int32_t i = 0; i < n_items; ++i) {
         const int32_t row = items_host[2 * i], id = items_host[2 * i + 1];
@@ -2504,14 +2575,14 @@ int nicnes_decode_path(nicnes_handle* h, int32_t B, int32_t count, int32_t* out_
     if (!h || !out_host || B < 1 || count < 1) return NICNES_ERR_INVALID;
     int G = 0, nslabs = 0, S = 0;
     decode_shape(h, B, count, &G, &nslabs, &S);
-    *out_host = h->wide ? 3 : S == 1 ? 0 : coop_fits(h, G, nslabs, S, count) ? 2 : 1;
+    *out_host = h->ln ? 4 : h->wide ? 3 : S == 1 ? 0 : coop_fits(h, G, nslabs, S, count) ? 2 : 1;
     return NICNES_OK;
 }
 
 int nicnes_set_decode_split(nicnes_handle* h, int32_t S, int32_t G) {
     if (!h || S < 0 || S > 64 || (G != 0 && G != 2 && G != 4)) return NICNES_ERR_INVALID;
     if (h->wide && (S > 1 || G == 2))
-        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): one workgroup per "
+        return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "one workgroup per "
                                                "member and 128-row slab, a forced split shape is not supported");
     HIPC(h, hipSetDevice(h->device));
     if (S > 0) {
@@ -2657,7 +2728,7 @@ int nicnes_es_free(nicnes_handle* h) {
 int nicnes_es_create(nicnes_handle* h, int32_t max_parents, int32_t max_elites) {
     if (!h || max_parents < 1 || max_elites < 1 || max_elites > max_parents) return NICNES_ERR_INVALID;
     if (h->wide)
-        return fail(h, NICNES_ERR_UNSUPPORTED, "wide models (rnn_size or input_encoding_size above 128): nic_es is not "
+        return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "nic_es is not "
                                                "supported");
     if (h->es) return fail(h, NICNES_ERR_INVALID, "nicnes_es_create: the handle has an ES state (nicnes_es_free first)");
     HIPC(h, hipSetDevice(h->device));

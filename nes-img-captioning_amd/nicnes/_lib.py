@@ -11,7 +11,7 @@ _NAMES = {ERR_INVALID: 'invalid argument', ERR_UNSUPPORTED: 'not supported', ERR
           ERR_NOMEM: 'out of device memory', ERR_FAULT: 'contained decode fault'}
 
 # every symbol include/nicnes.h declares (checked by tests/test_abi.py)
-EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_create', 'nicnes_destroy', 'nicnes_last_error',
+EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_param_offsets_ln', 'nicnes_test_ln_cell', 'nicnes_create', 'nicnes_destroy', 'nicnes_last_error',
            'nicnes_set_noise_table', 'nicnes_set_theta', 'nicnes_get_theta', 'nicnes_set_adam_state',
            'nicnes_get_adam_state', 'nicnes_set_batch', 'nicnes_set_df_table', 'nicnes_noise_indices',
            'nicnes_evaluate', 'nicnes_rank_weights', 'nicnes_grad_partial', 'nicnes_adam_step', 'nicnes_stats',
@@ -40,7 +40,8 @@ class NicnesConfig(ctypes.Structure):
     _fields_ = [('vocab_size', ctypes.c_int32), ('input_encoding_size', ctypes.c_int32),
                 ('rnn_size', ctypes.c_int32), ('fc_feat_size', ctypes.c_int32), ('seq_length', ctypes.c_int32),
                 ('max_batch', ctypes.c_int32), ('max_refs', ctypes.c_int32), ('max_members', ctypes.c_int32),
-                ('noise_len', ctypes.c_uint64), ('noise_seed', ctypes.c_uint64)]
+                ('noise_len', ctypes.c_uint64), ('noise_seed', ctypes.c_uint64),
+                ('layer_n', ctypes.c_int32), ('layer_n_affine', ctypes.c_int32)]
 
 
 class NicnesError(RuntimeError):
@@ -71,6 +72,8 @@ def lib(path=None):
     sig = {
         'nicnes_param_count': (i64, [vp]),
         'nicnes_param_offsets': (c.c_int, [vp, vp]),
+        'nicnes_param_offsets_ln': (c.c_int, [vp, vp]),
+        'nicnes_test_ln_cell': (c.c_int, [vp, vp, vp, vp, i32, vp, vp, vp]),
         'nicnes_create': (c.c_int, [vp, c.c_int, c.POINTER(vp)]),
         'nicnes_destroy': (c.c_int, [vp]),
         'nicnes_last_error': (c.c_char_p, [vp]),

@@ -8,10 +8,10 @@ Field names and defaults mirror
 A leading underscore disables a key ("_from_infos"), as in the reference JSON files. The engine
 implements the mscoco_nes.json hot path only: net 'fc_caption', every Fitness value (greedy, the
 greedy_* criteria, and the sampled sample / self_critical / sc_loss), model_options.safe_mutations
-'' / SM-G-SUM / SM-VECTOR / SM-PROPORTIONAL (nicnes.mutations), no vbn / layer_n; anything else
-raises NotSupported (nicnes_create returns NICNES_ERR_UNSUPPORTED for unsupported model sizes).
-model_options.rnn_size / input_encoding_size may each be 128, 256, 384 or 512; above 128 (is_wide) the
-sampled fitness values and SM-G-SUM raise NotSupported, as the engine refuses them there.
+'' / SM-G-SUM / SM-VECTOR / SM-PROPORTIONAL (nicnes.mutations), layer_n / layer_n_affine, no vbn; anything
+else raises NotSupported (nicnes_create returns NICNES_ERR_UNSUPPORTED for unsupported model sizes).
+model_options.rnn_size / input_encoding_size may each be 128, 256, 384 or 512; above 128 (is_wide), and with
+layer_n at every width, the sampled fitness values and SM-G-SUM raise NotSupported, as the engine refuses them there.
 """
 import json
 from collections import namedtuple
@@ -94,14 +94,22 @@ class ExperimentSpec:
         if self.fitness not in FITNESS:
             raise NotSupported("fitness %r: the engine implements %s (src/captioning/policies.py:22-61)"
                                % (po.fitness, ', '.join(FITNESS)))
-        if po.vbn or mo.vbn_e or mo.layer_n:
-            raise NotSupported('virtual batch norm / layer norm are not implemented by the engine')
+        if po.vbn or mo.vbn or mo.vbn_e:
+            raise NotSupported('virtual batch norm is not implemented by the engine (it normalises over the batch; '
+                               'layer_n, a function of one row, is)')
         m = self.mutation
         if m == 'SM-G-ABS':
             raise NotSupported("SM-G-ABS: the reference's _calc_abs_sensitivity raises AttributeError "
                                "(self.nb_params on Sensitivity, safe_mutations.py:125)")
         if m not in ('', 'SM-G-SUM', 'SM-VECTOR', 'SM-PROPORTIONAL'):
             raise NotSupported('safe_mutations %r (Mutation, src/algorithm/nets.py:16-21)' % m)
+        if mo.layer_n:
+            # a layer_n handle is refused what a wide one is (nicnes_set_fitness_mode, nicnes_sum_sensitivity)
+            if self.fitness in SAMPLED_FITNESS:
+                raise NotSupported('fitness %r: layer_n models decode greedily only (%s)'
+                                   % (self.fitness, ', '.join(GREEDY_FITNESS)))
+            if m == 'SM-G-SUM':
+                raise NotSupported('SM-G-SUM: the sensitivity is not implemented for layer_n models')
         if is_wide(mo):
             # what the engine refuses at wide dims (nicnes_set_fitness_mode, nicnes_sum_sensitivity) is refused here,
             # never ignored
@@ -158,4 +166,5 @@ class ExperimentSpec:
         return dict(vocab_size=int(mo.vocab_size), input_encoding_size=int(mo.input_encoding_size or 128),
                     rnn_size=int(mo.rnn_size or 128), fc_feat_size=int(mo.fc_feat_size or 2048),
                     seq_length=int(mo.seq_length or 16), max_batch=int(max_batch or self.batch_size),
-                    max_members=int(max_members), noise_len=int(noise_len), noise_seed=int(noise_seed))
+                    max_members=int(max_members), noise_len=int(noise_len), noise_seed=int(noise_seed),
+                    layer_n=bool(mo.layer_n), layer_n_affine=bool(mo.layer_n and mo.layer_n_affine))

@@ -56,15 +56,23 @@ class Engine:
 
     def __init__(self, vocab_size=9487, input_encoding_size=128, rnn_size=128, fc_feat_size=2048,  # noqa: E501
                  seq_length=SEQ_LENGTH, max_batch=128, max_refs=None, max_members=512, noise_len=1 << 27,
-                 noise_seed=0, device=0, lib_path=None):
+                 noise_seed=0, device=0, lib_path=None, layer_n=False, layer_n_affine=False):
         self.L = _lib.lib(lib_path)
         self.device = torch.device('cuda', device)
         self.cfg = NicnesConfig(vocab_size, input_encoding_size, rnn_size, fc_feat_size, seq_length, max_batch,
-                                max_refs or 8 * max_batch, max_members, noise_len, noise_seed)
+                                max_refs or 8 * max_batch, max_members, noise_len, noise_seed,
+                                int(bool(layer_n)), int(bool(layer_n_affine)))
+        # layer_n_affine without layer_n is ignored, as the reference ignores it
+        self.layer_n, self.layer_n_affine = bool(layer_n), bool(layer_n and layer_n_affine)
         self.D = int(self.L.nicnes_param_count(ctypes.byref(self.cfg)))
         off = (ctypes.c_int64 * 10)()
         check(self.L.nicnes_param_offsets(ctypes.byref(self.cfg), off), None, 'nicnes_param_offsets')
         self.offsets = list(off)
+        self.ln_offsets = None           # layer_n_affine: the six tail tensors' offsets + D
+        if self.layer_n_affine:
+            off7 = (ctypes.c_int64 * 7)()
+            check(self.L.nicnes_param_offsets_ln(ctypes.byref(self.cfg), off7), None, 'nicnes_param_offsets_ln')
+            self.ln_offsets = list(off7)
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             check(self.L.nicnes_create(ctypes.byref(self.cfg), device, ctypes.byref(h)), None, 'nicnes_create')
@@ -564,11 +572,25 @@ class Engine:
         return out
 
     def decode_path(self, B=None, count=1):
-        """'fused', 'split', 'coop' or 'wide': the decode path an evaluate of `count` members would take ('wide': a model
-        with rnn_size or input_encoding_size above 128, whatever B and count)."""
+        """'fused', 'split', 'coop', 'wide' or 'ln': the decode path an evaluate of `count` members would take ('wide': a
+        model with rnn_size or input_encoding_size above 128, 'ln': a layer_n model, both whatever B and count)."""
         out = ctypes.c_int32()
         check(self.L.nicnes_decode_path(self.h, int(B or self.B), int(count), ctypes.byref(out)), self.h, 'decode_path')
-        return ('fused', 'split', 'coop', 'wide')[out.value]
+        return ('fused', 'split', 'coop', 'wide', 'ln')[out.value]
+
+    def test_ln_cell(self, x, h, c):
+        """One layer-norm LSTM cell of theta itself on rows x [rows, E], h, c [rows, R] (rows <= 128) by the decode's
+        device function (nicnes_test_ln_cell) -> (h', c') as numpy. No decode may run beside it."""
+        xr, hr, cr = (self._dev(np.asarray(a, np.float32), torch.float32) for a in (x, h, c))
+        rows = int(xr.shape[0])
+        assert xr.shape == (rows, self.cfg.input_encoding_size)
+        assert hr.shape == (rows, self.cfg.rnn_size) and cr.shape == hr.shape
+        ho, co = torch.empty_like(hr), torch.empty_like(cr)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_test_ln_cell(self.h, _ptr(xr), _ptr(hr), _ptr(cr), rows, _ptr(ho), _ptr(co),
+                                             self._stream()), self.h, 'test_ln_cell')
+        torch.cuda.synchronize(self.device)
+        return ho.cpu().numpy(), co.cpu().numpy()
 
     def decode_shape(self, B=None, count=1):
         """(G, slabs, S) an evaluate of `count` members would use."""

@@ -28,15 +28,22 @@ NESResult = namedtuple('NESResult', field_names=result_fields, defaults=(None,) 
 
 PARAM_NAMES = ['img_embed.weight', 'img_embed.bias', 'embed.weight', 'logit.weight', 'logit.bias',
                'core.i2h.weight', 'core.i2h.bias', 'core.h2h.weight', 'core.h2h.bias']
+# layer_n with layer_n_affine: the reference's parameters() appends these (LSTMCore registers its LayerNorms last)
+LN_PARAM_NAMES = ['core.i2h_ln.weight', 'core.i2h_ln.bias', 'core.h2h_ln.weight', 'core.h2h_ln.bias',
+                  'core.c_ln.weight', 'core.c_ln.bias']
 
 
 # ---------------------------------------------------------------- theta <-> state_dict ----------
 def param_shapes(engine):
     c = engine.cfg
     V1, E, R, F = c.vocab_size + 1, c.input_encoding_size, c.rnn_size, c.fc_feat_size
-    return OrderedDict([('img_embed.weight', (E, F)), ('img_embed.bias', (E,)), ('embed.weight', (V1, E)),
-                        ('logit.weight', (V1, R)), ('logit.bias', (V1,)), ('core.i2h.weight', (5 * R, E)),
-                        ('core.i2h.bias', (5 * R,)), ('core.h2h.weight', (5 * R, R)), ('core.h2h.bias', (5 * R,))])
+    shapes = OrderedDict([('img_embed.weight', (E, F)), ('img_embed.bias', (E,)), ('embed.weight', (V1, E)),
+                          ('logit.weight', (V1, R)), ('logit.bias', (V1,)), ('core.i2h.weight', (5 * R, E)),
+                          ('core.i2h.bias', (5 * R,)), ('core.h2h.weight', (5 * R, R)), ('core.h2h.bias', (5 * R,))])
+    if getattr(c, 'layer_n', 0) and getattr(c, 'layer_n_affine', 0):
+        for name in LN_PARAM_NAMES:
+            shapes[name] = (R,) if '.c_ln.' in name else (5 * R,)
+    return shapes
 
 
 def vector_from_state_dict(sd, shapes):
@@ -44,7 +51,9 @@ def vector_from_state_dict(sd, shapes):
     parts = []
     for name, shp in shapes.items():
         if name not in sd:
-            raise KeyError('state_dict lacks %r (vbn / layer-norm models are not supported)' % name)
+            raise KeyError('state_dict lacks %r (%s)' % (
+                name, 'the engine was created with layer_n_affine: the checkpoint must come from such a model'
+                if '_ln.' in name else 'vbn models are not supported'))
         t = sd[name]
         t = t.detach().cpu() if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t))
         if tuple(t.shape) != tuple(shp):

@@ -18,14 +18,19 @@ from .engine import df_table_arrays
 
 
 class Dims:
-    def __init__(self, vocab_size=9487, E=128, R=128, F=2048, T=16):
+    def __init__(self, vocab_size=9487, E=128, R=128, F=2048, T=16, layer_n=False, layer_n_affine=False):
         self.vocab_size, self.V1, self.E, self.R, self.F, self.T = vocab_size, vocab_size + 1, E, R, F, T
+        self.layer_n, self.layer_n_affine = bool(layer_n), bool(layer_n and layer_n_affine)
 
     def shapes(self):
         V1, E, R, F = self.V1, self.E, self.R, self.F
-        return [('img_embed.weight', (E, F)), ('img_embed.bias', (E,)), ('embed.weight', (V1, E)),
-                ('logit.weight', (V1, R)), ('logit.bias', (V1,)), ('core.i2h.weight', (5 * R, E)),
-                ('core.i2h.bias', (5 * R,)), ('core.h2h.weight', (5 * R, R)), ('core.h2h.bias', (5 * R,))]
+        s = [('img_embed.weight', (E, F)), ('img_embed.bias', (E,)), ('embed.weight', (V1, E)),
+             ('logit.weight', (V1, R)), ('logit.bias', (V1,)), ('core.i2h.weight', (5 * R, E)),
+             ('core.i2h.bias', (5 * R,)), ('core.h2h.weight', (5 * R, R)), ('core.h2h.bias', (5 * R,))]
+        if self.layer_n_affine:          # the reference's names, appended in its registration order
+            s += [('core.i2h_ln.weight', (5 * R,)), ('core.i2h_ln.bias', (5 * R,)), ('core.h2h_ln.weight', (5 * R,)),
+                  ('core.h2h_ln.bias', (5 * R,)), ('core.c_ln.weight', (R,)), ('core.c_ln.bias', (R,))]
+        return s
 
     @property
     def D(self):
@@ -37,7 +42,9 @@ def init_theta(dims, seed=0, gain=1.0, bias_std=0.0):
     rng = np.random.Generator(np.random.PCG64(seed))
     parts = []
     for name, shp in dims.shapes():
-        if name.endswith('weight'):
+        if '_ln.' in name:     # initialize_params leaves every tensor whose name contains 'ln' at torch's default
+            parts.append(np.full(int(np.prod(shp)), 1.0 if name.endswith('weight') else 0.0, np.float32))
+        elif name.endswith('weight'):
             std = gain * np.sqrt(2.0 / float(shp[1] + shp[0]))
             parts.append((rng.standard_normal(shp) * std).astype(np.float32).ravel())
         elif bias_std > 0:
@@ -112,7 +119,7 @@ def setup_engine_workload(engine, B=128, theta_seed=0, fc_seed=1234, bu=False, n
     with set_batches; fc / gts / base then cover all batches * B images in batch order.
     Returns dict(theta32, fc, gts, df, ref_len_raw, base)."""
     dims = Dims(engine.cfg.vocab_size, engine.cfg.input_encoding_size, engine.cfg.rnn_size,
-                engine.cfg.fc_feat_size, engine.cfg.seq_length)
+                engine.cfg.fc_feat_size, engine.cfg.seq_length, engine.cfg.layer_n, engine.cfg.layer_n_affine)
     if noise is None:
         noise = noise_table(engine.cfg.noise_len)
     engine.set_noise_table(noise)
