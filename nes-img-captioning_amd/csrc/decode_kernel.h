@@ -187,20 +187,17 @@ extern "C" hipError_t nicnes_launch_beam_decode(const DecodeParams* p, int32_t* 
 extern "C" hipError_t nicnes_launch_test_beam_select(const float* lp, const double* score, const int32_t* live, int n_img,
                                                      int K, int V1, int32_t* out, hipStream_t stream);
 // the wide greedy decode (decode_wide_kernels.hip): E = input_encoding_size, R = rnn_size, each in {128, 256, 384, 512};
-// one launch of member_count x nslabs workgroups (p->G == 4, p->S == 1, greedy, no MutHead), exact exp-sum; p->scratch
-// holds nicnes_wide_scratch_floats(member_count * nslabs, E, R) floats. evs / kinds / n_launch as nicnes_launch_decode
-// (one launch, kind DK_STEPS). nicnes_decode_wide_init: per device, once per handle (its dynamic LDS is above 64 KB).
+// one launch of member_count x nslabs workgroups (p->G == 4, p->S == 1, greedy, no MutHead), exact exp-sum. One step-loop
+// frame, two cells: the plain LSTM cell, or with ln != 0 the layer-norm cell of layer_n models (decode_ln_kernels.hip),
+// whose lane scratch is larger. tail6: the theta offsets of the six affine tensors (i2h_ln weight, bias, h2h_ln weight,
+// bias, c_ln weight, bias), NULL without layer_n_affine. p->scratch holds nicnes_wide_scratch_floats(member_count * nslabs,
+// E, R, ln) floats. evs / kinds / n_launch as nicnes_launch_decode (one launch, kind DK_STEPS). nicnes_decode_wide_init:
+// per device, once per handle (the dynamic LDS of both kernels and of the test entry below is above 64 KB).
 extern "C" hipError_t nicnes_decode_wide_init();
-extern "C" size_t nicnes_wide_scratch_floats(int64_t workgroups, int E, int R);
-extern "C" hipError_t nicnes_launch_decode_wide(const DecodeParams* p, int E, int R, int member_count, int nslabs,
-                                                hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch);
-// the layer-norm greedy decode (decode_ln_kernels.hip; layer_n models at every supported width): the wide launch's shape
-// and rules with its own, larger lane scratch (nicnes_ln_scratch_floats). tail6: the theta offsets of the six affine
-// tensors (i2h_ln weight, bias, h2h_ln weight, bias, c_ln weight, bias), NULL without layer_n_affine.
-extern "C" hipError_t nicnes_decode_ln_init();
-extern "C" size_t nicnes_ln_scratch_floats(int64_t workgroups, int E, int R);
-extern "C" hipError_t nicnes_launch_decode_ln(const DecodeParams* p, int E, int R, const int64_t* tail6, int member_count,
-                                              int nslabs, hipStream_t stream, hipEvent_t* evs, int* kinds, int* n_launch);
+extern "C" size_t nicnes_wide_scratch_floats(int64_t workgroups, int E, int R, int ln);
+extern "C" hipError_t nicnes_launch_decode_wide(const DecodeParams* p, int E, int R, int ln, const int64_t* tail6,
+                                                int member_count, int nslabs, hipStream_t stream, hipEvent_t* evs,
+                                                int* kinds, int* n_launch);
 // test entry (nicnes_test_ln_cell): one layer-norm cell of theta itself (p->noise: D zeros) on rows <= 128 given rows
 // xin [rows, E], hin [rows, R], cin [rows, R] by the decode's device function; p->scratch holds one workgroup's lane scratch
 extern "C" hipError_t nicnes_launch_test_ln_cell(const DecodeParams* p, int E, int R, const int64_t* tail6,

@@ -3786,10 +3786,8 @@ extern "C" hipError_t nicnes_launch_test_logit_chain(const DecodeParams* p, uint
 
 // the beam-search decode (evaluation only): its kernels and launches, compiled in this unit ahead of its last kernel
 #include "beam_kernels.hip"
-// the greedy decode of models wider than 128 units, likewise
+// the greedy decode of models wider than 128 units and (decode_ln_kernels.hip, #included there) of layer_n models, likewise
 #include "decode_wide_kernels.hip"
-// the greedy decode of layer_n models on the wide kernel's structure, likewise
-#include "decode_ln_kernels.hip"
 
 // ========== test entry: given (row, id) items through the screened decode's certify_tiles ======================
 // One workgroup of the decode's shape. hin [128, 128] is laid out as its eight waves' lane scratch (wave w: sign w >> 2,

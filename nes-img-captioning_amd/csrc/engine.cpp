@@ -123,7 +123,7 @@ struct nicnes_handle {
     bool sc_valid = false;
     bool wide = false;                // E or R above 128 (or the test hook NICNES_DECODE_WIDE=1): every decode request goes
                                       // to the wide launcher (decode_wide_kernels.hip): 128-row slabs, one stream
-    bool ln = false;                  // cfg.layer_n: a wide handle whose launcher is the layer-norm one
+    bool ln = false;                  // cfg.layer_n: a wide handle whose launch runs the layer-norm cell
                                       // (decode_ln_kernels.hip), at every width; ln_off: the six affine tensors' offsets
     bool ln_affine = false;           // cfg.layer_n_affine (with layer_n): theta carries the six tensors at its tail
     int64_t ln_off[6] = {0, 0, 0, 0, 0, 0};
@@ -495,12 +495,6 @@ int alloc_refs(nicnes_handle* h, int max_refs) {
 
 // Buffers sized by the batch: per-image n-gram tables, tokens / log-probs / row scores of a launch,
 // decode lane scratch, alive flags and partial states.
-// lane scratch of `workgroups` workgroups of the wide path's launcher (the layer-norm one on a layer_n handle)
-size_t wide_scratch_floats(const nicnes_handle* h, int64_t workgroups) {
-    const int E = h->cfg.input_encoding_size, R = h->cfg.rnn_size;
-    return h->ln ? nicnes_ln_scratch_floats(workgroups, E, R) : nicnes_wide_scratch_floats(workgroups, E, R);
-}
-
 int alloc_batch(nicnes_handle* h, int max_batch) {
     void* old[] = {h->seq, h->lp, h->row_scores, h->dscratch, h->alive, h->part};
     for (void* q : old)
@@ -520,7 +514,8 @@ int alloc_batch(nicnes_handle* h, int max_batch) {
     if (!rc) rc = dalloc(h, &h->lp, MM * 2 * MB * T);
     if (!rc) rc = dalloc(h, &h->row_scores, MM * 2 * MB);
     // (the wide path: its lane scratch is sized from (E, R), one workgroup per member and 128-row slab)
-    const size_t wide_fl = h->wide ? wide_scratch_floats(h, (int64_t)MM * nslabs_of((int)MB, 4)) : 0;
+    const size_t wide_fl = !h->wide ? 0 : nicnes_wide_scratch_floats((int64_t)MM * nslabs_of((int)MB, 4),
+                                                                     h->cfg.input_encoding_size, h->cfg.rnn_size, h->ln);
     if (!rc) rc = dalloc(h, &h->dscratch, std::max(nicnes_decode_scratch_floats((int)MM, rw), wide_fl));
     if (!rc) rc = dalloc(h, &h->coop_ctr, MM * (size_t)ns * COOP_CTR_STRIDE);
     if (!rc) rc = dalloc(h, &h->alive, 3 * (size_t)h->alive_stride);
@@ -653,7 +648,6 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
     }
     if (!rc && nicnes_decode_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_init");
     if (!rc && nicnes_decode_wide_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_wide_init");
-    if (!rc && nicnes_decode_ln_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_ln_init");
     if (!rc && (nicnes_decode_occupancy(&h->coop_occ, &h->sample_occ) != hipSuccess || h->coop_occ < 1 ||
                 h->sample_occ < 1))
         rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_occupancy");
@@ -1445,13 +1439,9 @@ static int launch_decode_parts(nicnes_handle* h, const DecodeParams& p, const Mu
         if (pa || mh.mode || sa.cap || p.sample_u)
             return -fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "greedy decode "
                                                     "only");
-        if (h->ln)
-            HIPN(nicnes_launch_decode_ln(&p, h->cfg.input_encoding_size, h->cfg.rnn_size,
-                                         h->ln_affine ? h->ln_off : nullptr, count, nslabs, s, timed ? h->dev : nullptr,
-                                         h->dev_kind, n_ev));
-        else
-            HIPN(nicnes_launch_decode_wide(&p, h->cfg.input_encoding_size, h->cfg.rnn_size, count, nslabs, s,
-                                           timed ? h->dev : nullptr, h->dev_kind, n_ev));
+        HIPN(nicnes_launch_decode_wide(&p, h->cfg.input_encoding_size, h->cfg.rnn_size, h->ln,
+                                       h->ln_affine ? h->ln_off : nullptr, count, nslabs, s, timed ? h->dev : nullptr,
+                                       h->dev_kind, n_ev));
     } else if (nstr > 1) {
         // members split evenly over the caller's stream and nstr - 1 engine streams; the parts share
         // nothing but the fallback counter (an atomic). No per-launch events: the launches overlap
@@ -1842,8 +1832,9 @@ static int split_grow(nicnes_handle* h, nicnes_split* sp, int n_pm, int64_t n_lw
         // a pseudo-member is one 128-row slab or two 64-row slabs: 8 row waves of lane scratch, <= 2 workgroups
         int rc = dalloc(h, &sp->seq, rows * T);
         if (!rc) rc = dalloc(h, &sp->lp, rows * T);
-        if (!rc) rc = dalloc(h, &sp->scratch, std::max(nicnes_decode_scratch_floats(n_pm, 8),
-                                                       h->wide ? wide_scratch_floats(h, n_pm) : (size_t)0));
+        const size_t wide_fl = !h->wide ? 0 : nicnes_wide_scratch_floats(n_pm, h->cfg.input_encoding_size,
+                                                                         h->cfg.rnn_size, h->ln);
+        if (!rc) rc = dalloc(h, &sp->scratch, std::max(nicnes_decode_scratch_floats(n_pm, 8), wide_fl));
         if (!rc) rc = dalloc(h, &sp->alive, 3 * 2 * PM);
         if (!rc) rc = dalloc(h, &sp->coop_ctr, 2 * PM * COOP_CTR_STRIDE);
         if (!rc) rc = dalloc(h, &sp->zero_idx, PM);
