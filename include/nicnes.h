@@ -452,8 +452,18 @@ int nicnes_set_decode_coop(nicnes_handle* h, int32_t mode);
  * out (device, D floats) = sqrt(sum_k J[k, :]^2) / rows, clamped to >= underflow and divided by it
  * (safe_mutations.py:63-65; underflow <= 0: the raw vector). The greedy tokens come from the engine's
  * bit-exact decode; the K = V1 / 100 + 1 backward passes run batched on the GPU, so the vector agrees
- * with the reference's to fp32 rounding (a stated tolerance), not bit for bit. Asynchronous on stream. */
+ * with the reference's to fp32 rounding (a stated tolerance), not bit for bit. Asynchronous on stream.
+ * Limit: rows <= 819 (the embedding kernels list the 5 * rows token cells in LDS, 4096 at most), whatever
+ * max_batch is: NICNES_ERR_UNSUPPORTED above it, before anything is enqueued. */
 int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, float* out_dev, void* stream);
+/* The kernels the last sensitivity run of this handle chose (nicnes_sum_sensitivity or nicnes_sensitivity_es, which
+ * share the work buffers; after nicnes_sensitivity_es: its last slot's run). Host bookkeeping only: no kernel, no
+ * synchronisation. out_host[0]: bit 0 logit.weight square sums on the LDS-resident kernel (rows <= 128), bit 1 the
+ * backward recurrence fused into one launch per cell (i2h / h2h weights 16-byte aligned), bit 2 gate and image weight
+ * square sums on the k-invariant-B kernel (K <= 96), bit 3 embedding rows in two passes (K <= 96); a clear bit is the
+ * general tile / range kernel. out_host[1], out_host[2]: the run's tile products launched with 16-byte and with
+ * scalar operand loads. NICNES_ERR_INVALID before the first run (and after one that failed while it enqueued). For tests and reports. */
+int nicnes_sens_paths(nicnes_handle* h, int32_t* out_host);
 /* the decode path an evaluate of `count` members of a B-image batch would take: 0 fused (one launch,
  * one workgroup per member slab), 1 split (two launches per step), 2 coop (the split shape in one launch), 3 wide (a
  * model with input_encoding_size or rnn_size above 128, or NICNES_DECODE_WIDE=1: one launch, one workgroup per member
@@ -595,6 +605,7 @@ int nicnes_set_mutation_divide_es(nicnes_handle* h);
  * run one after the other on `stream`. slots_host [n_slots] (HOST). The table is allocated at the first call
  * (synchronising then; its pad columns [D, Dp) are written 1.0 once); afterwards the call only enqueues.
  * NICNES_ERR_INVALID: a slot outside [0, parent count), rows outside [1, B], underflow <= 0, no batch held.
+ * NICNES_ERR_UNSUPPORTED: rows > 819 (nicnes_sum_sensitivity's limit), before anything is allocated or enqueued.
  * A row stops being valid when nicnes_es_set_parent rewrites its slot, and every row does at nicnes_es_advance (the
  * tables swap). Leaves shared mode (below). */
 int nicnes_sensitivity_es(nicnes_handle* h, const int32_t* slots_host, int32_t n_slots, int32_t rows, float underflow,

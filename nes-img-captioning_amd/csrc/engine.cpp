@@ -2064,8 +2064,22 @@ int nicnes_test_beam_select(nicnes_handle* h, const float* lp_dev, const double*
 
 // The SM-G-SUM sensitivity of `theta` (the handle's theta32, or a parent row of nicnes_sensitivity_es) on the first
 // `rows` images of the batch held, into out [D]
+static const int SENS_L = 5;                                       // forward_for_sensitivity's length (nets.py:22)
+
+// the embedding kernels list every (cell, row) pair in LDS: SENS_L * rows <= NICNES_SENS_MAX_PAIRS, refused by name
+// before anything is allocated or enqueued (nicnes_sens_run keeps its own check)
+static int sens_rows_fit(nicnes_handle* h, int32_t rows) {
+    const int max_rows = NICNES_SENS_MAX_PAIRS / SENS_L;
+    if (rows > max_rows)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "the SM-G-SUM sensitivity takes rows <= " + std::to_string(max_rows) +
+                                               " (" + std::to_string(SENS_L) + " * rows <= " +
+                                               std::to_string(NICNES_SENS_MAX_PAIRS) + " token cells), got " +
+                                               std::to_string(rows));
+    return NICNES_OK;
+}
+
 static int sens_of_theta(nicnes_handle* h, const float* theta, int32_t rows, float underflow, float* out, hipStream_t s) {
-    const int L = 5, split = 100;                                  // forward_for_sensitivity defaults (nets.py:22)
+    const int L = SENS_L, split = 100;                             // forward_for_sensitivity defaults (nets.py:22)
     if (!h->sens_tok) {
         HIPC(h, hipDeviceSynchronize());
         int rc = dalloc(h, &h->sens_tok, (size_t)2 * h->cfg.max_batch * (L - 1));
@@ -2105,8 +2119,16 @@ int nicnes_sum_sensitivity(nicnes_handle* h, int32_t rows, float underflow, floa
     if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
     if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
     if (rows > h->B) return fail(h, NICNES_ERR_INVALID, "rows beyond the batch held");
+    if (int rc = sens_rows_fit(h, rows)) return rc;
     HIPC(h, hipSetDevice(h->device));
     return sens_of_theta(h, h->theta32, rows, underflow, out, (hipStream_t)stream);
+}
+
+int nicnes_sens_paths(nicnes_handle* h, int32_t* out_host) {
+    if (!h || !out_host) return NICNES_ERR_INVALID;
+    if (!h->sens || nicnes_sens_last_paths(h->sens, out_host))
+        return fail(h, NICNES_ERR_INVALID, "nicnes_sum_sensitivity or nicnes_sensitivity_es first");
+    return NICNES_OK;
 }
 
 int nicnes_rank_weights(nicnes_handle* h, const double* fitness, int32_t P, double* cr_out, float* w_out, void* stream) {
@@ -2832,6 +2854,7 @@ int nicnes_sensitivity_es(nicnes_handle* h, const int32_t* slots_host, int32_t n
     if (!slots_host || n_slots < 1) return NICNES_ERR_INVALID;
     if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
     if (rows < 1 || rows > h->B) return fail(h, NICNES_ERR_INVALID, "rows out of [1, B] of the batch held");
+    if (int rc = sens_rows_fit(h, rows)) return rc;
     if (!(underflow > 0.f)) return fail(h, NICNES_ERR_INVALID, "underflow must be > 0 (calc_sensitivity divides by it)");
     for (int k = 0; k < n_slots; ++k)
         if (slots_host[k] < 0 || slots_host[k] >= es->n_parents)

@@ -766,7 +766,7 @@ __global__ void sens_sum_parts(const float* parts, int nparts, int64_t n, float*
 // pair p = (i - 1) Bs + b: if p is its token's first pair, the token's pairs are listed in LDS and the block adds
 // G_k[t, e]^2 over k in range kc into out[kc][t E + e] (thread e; partial rows summed by sens_finish).
 // dX_all [K][L + 1][Bs][E]; npair <= EMB_MAXP.
-#define EMB_MAXP 4096
+#define EMB_MAXP NICNES_SENS_MAX_PAIRS
 #define EMB_KC 8
 // the pairs grouped by token, once per vector (one block): keys token * EMB_MAXP + pair sorted in LDS (bitonic), so a
 // token's pairs are contiguous and in increasing pair order. runs[0] = the number of tokens fed, runs[1 + u] = the
@@ -996,6 +996,9 @@ struct SensWork {
     int* elist = nullptr;   // [EMB_MAXP] dX rows in token-then-pair order
     int* rchunk = nullptr;  // [EMB_MAXP + 2] each run's first chunk (sens_emb_part)
     float* echunk = nullptr;  // [chunks][K][E] the chunks' sums
+    // what the last run chose (nicnes_sens_last_paths): SENS_PATH_* bits (-1 before the first run), and the gemm launches
+    // with 16-byte and with scalar operand loads
+    int paths = -1, gemm_v4 = 0, gemm_scalar = 0;
 };
 
 namespace {
@@ -1086,9 +1089,10 @@ inline bool tile_fits4(const Strided& A, const TileArgs& t) {
 }
 
 template <class AOp>
-void gemm(const AOp& A, const TileArgs& t, int batch, hipStream_t st) {
+void gemm(SensWork* w, const AOp& A, const TileArgs& t, int batch, hipStream_t st) {
     if constexpr (std::is_same<AOp, Strided>::value) {
         if (tile_fits4(A, t)) {
+            ++w->gemm_v4;
             // 64-long chunks: with 16-byte loads the registers allow them (4 + 4 float4 per thread), and a wave's 32
             // MFMAs per chunk cover the next chunk's loads (the image projection's 2048-long chains: 32 chunks, not 64)
             hipLaunchKernelGGL((sens_tile<Strided, false, 64, true>), dim3(blocks(t.M, TM), blocks(t.N, TN), batch),
@@ -1096,6 +1100,7 @@ void gemm(const AOp& A, const TileArgs& t, int batch, hipStream_t st) {
             return;
         }
     }
+    ++w->gemm_scalar;
     hipLaunchKernelGGL((sens_tile<AOp, false>), dim3(blocks(t.M, TM), blocks(t.N, TN), batch), dim3(256), 0, st, A, t);
 }
 
@@ -1129,6 +1134,8 @@ extern "C" int nicnes_sens_run(SensWork* w, const SensParams* p, hipStream_t st)
     if (!w || !p || p->Bs < 1 || p->L < 1 || p->split < 1) return 1;
     if (p->E > 256 || p->R > 256) return 1;                     // thread-per-column kernels
     if ((int64_t)p->L * p->Bs > EMB_MAXP) return 1;             // sens_emb_sq's pair list
+    w->paths = -1;                                               // valid again once every launch below is enqueued
+    w->gemm_v4 = w->gemm_scalar = 0;
     if (grow(w, p) != hipSuccess) return 3;
     const int Bs = p->Bs, E = p->E, R = p->R, F = p->F, V = p->V1, K = p->K, L = p->L, G5 = 5 * R;
     const int64_t D = p->D, L1 = L + 1;
@@ -1145,22 +1152,22 @@ extern "C" int nicnes_sens_run(SensWork* w, const SensParams* p, hipStream_t st)
 
     // ---- forward: image cell, then L token cells (forward_for_sensitivity, nets.py:48-64); C = A B with
     // A row-major [rows, red] and B = W^T of a row-major [out, in] weight
-    gemm(sa(p->fc, 0, F, 1), fwd(targs(Bs, E, F, Wimg, 0, 1, F, Xs(0), 0, E, 1), bimg), 1, st);   // img_embed
+    gemm(w, sa(p->fc, 0, F, 1), fwd(targs(Bs, E, F, Wimg, 0, 1, F, Xs(0), 0, E, 1), bimg), 1, st);   // img_embed
     for (int i = 0; i <= L; ++i) {
         if (i >= 1)
             hipLaunchKernelGGL(sens_embed_gather, dim3(Bs), dim3(E), 0, st, Xs(i), Wemb, p->tok, p->tok_stride,
                                tok_col(i), Bs, E);
-        gemm(sa(Xs(i), 0, E, 1), fwd(targs(Bs, G5, E, Wi, 0, 1, E, Ss(i), 0, G5, 1), bi), 1, st);          // i2h
-        if (i >= 1) gemm(sa(Hs(i - 1), 0, R, 1), fwd(targs(Bs, G5, R, Wh, 0, 1, R, w->Sh, 0, G5, 1), bh), 1, st);   // h2h
+        gemm(w, sa(Xs(i), 0, E, 1), fwd(targs(Bs, G5, E, Wi, 0, 1, E, Ss(i), 0, G5, 1), bi), 1, st);          // i2h
+        if (i >= 1) gemm(w, sa(Hs(i - 1), 0, R, 1), fwd(targs(Bs, G5, R, Wh, 0, 1, R, w->Sh, 0, G5, 1), bh), 1, st);   // h2h
         hipLaunchKernelGGL(sens_cell_fwd, dim3(blocks((int64_t)Bs * R, 256)), dim3(256), 0, st, Ss(i),
                            i ? (const float*)w->Sh : (const float*)nullptr, bh,
                            i ? (const float*)Cs(i - 1) : (const float*)nullptr, Cs(i), Hs(i), Bs, R);
         if (p->tok_internal && i >= 1 && i < L) {      // the token fed to cell i + 1 (nets.py:60-63)
-            gemm(sa(Hs(i), 0, R, 1), fwd(targs(Bs, V, R, Wl, 0, 1, R, w->Z, 0, V, 1), bl), 1, st);
+            gemm(w, sa(Hs(i), 0, R, 1), fwd(targs(Bs, V, R, Wl, 0, 1, R, w->Z, 0, V, 1), bl), 1, st);
             hipLaunchKernelGGL(sens_greedy, dim3(Bs), dim3(ROW_T), 0, st, w->Z, V, p->tok, p->tok_stride, i - 1);
         }
     }
-    gemm(sa(Hs(L), 0, R, 1), fwd(targs(Bs, V, R, Wl, 0, 1, R, w->Z, 0, V, 1), bl), 1, st);             // logit
+    gemm(w, sa(Hs(L), 0, R, 1), fwd(targs(Bs, V, R, Wl, 0, 1, R, w->Z, 0, V, 1), bl), 1, st);             // logit
     hipLaunchKernelGGL(sens_logsoftmax, dim3(Bs), dim3(ROW_T), 0, st, w->Z, w->LP, w->P, V);
 
     // ---- the K backward passes at once
@@ -1193,7 +1200,7 @@ extern "C" int nicnes_sens_run(SensWork* w, const SensParams* p, hipStream_t st)
             sqsum(dz, targs(V, R, Bs, Hs(L), 0, R, 1, part + p->off_log_w, D, R, 1), K, SENS_NZ, st);
     }
     // logit.bias: PS = p^T S over the batch, then the group terms
-    gemm(sa(w->P, 0, 1, V), targs(V, K, Bs, w->SG, 0, K, 1, w->PS, 0, 1, V), 1, st);          // PS^T [K, V]
+    gemm(w, sa(w->P, 0, 1, V), targs(V, K, Bs, w->SG, 0, K, 1, w->PS, 0, 1, V), 1, st);          // PS^T [K, V]
     hipLaunchKernelGGL(sens_logb_sq, dim3(blocks(V, 64)), dim3(256), 0, st, w->LP, w->IG, w->PS, Bs, V, K, p->split,
                        part + p->off_log_b);
     // dH of the last cell: p Wl once (split over the vocabulary: nsp partial products, summed in order), then the
@@ -1203,16 +1210,16 @@ extern "C" int nicnes_sens_run(SensWork* w, const SensParams* p, hipStream_t st)
         for (int d = 32; d > 1; --d)
             if (V % d == 0 && V / d >= TR_MIN) { nsp = d; break; }
         const int cl = V / nsp;
-        gemm(sa(w->P, cl, V, 1), targs(Bs, R, cl, Wl, (int64_t)cl * R, R, 1, w->PWp, (int64_t)Bs * R, R, 1), nsp, st);
+        gemm(w, sa(w->P, cl, V, 1), targs(Bs, R, cl, Wl, (int64_t)cl * R, R, 1, w->PWp, (int64_t)Bs * R, R, 1), nsp, st);
         hipLaunchKernelGGL(sens_sum_parts, dim3(blocks((int64_t)Bs * R, 256)), dim3(256), 0, st, w->PWp, nsp,
                            (int64_t)Bs * R, w->PW);
     }
     {
         const int sp = p->split, kfull = V / sp, rem = V - kfull * sp;
         if (kfull > 0)           // the full groups: O_k [Bs, R] = lp[:, k sp .. + sp] Wl[k sp .. + sp, :]
-            gemm(sa(w->LP, sp, V, 1), targs(Bs, R, sp, Wl, (int64_t)sp * R, R, 1, w->dH, (int64_t)Bs * R, R, 1), kfull, st);
+            gemm(w, sa(w->LP, sp, V, 1), targs(Bs, R, sp, Wl, (int64_t)sp * R, R, 1, w->dH, (int64_t)Bs * R, R, 1), kfull, st);
         if (rem > 0)             // the last group's rows inside the vocabulary
-            gemm(sa(w->LP + (int64_t)kfull * sp, 0, V, 1),
+            gemm(w, sa(w->LP + (int64_t)kfull * sp, 0, V, 1),
                  targs(Bs, R, rem, Wl + (int64_t)kfull * sp * R, 0, R, 1, w->dH + (int64_t)kfull * Bs * R, 0, R, 1), 1, st);
         const int kown = std::min(K, kfull + (rem > 0 ? 1 : 0));
         hipLaunchKernelGGL(sens_dh_logit, dim3(blocks((int64_t)K * Bs * R, 256)), dim3(256), 0, st, w->IG, w->SG, w->PW,
@@ -1220,6 +1227,9 @@ extern "C" int nicnes_sens_run(SensWork* w, const SensParams* p, hipStream_t st)
     }
     if (hipMemsetAsync(w->dC, 0, (size_t)K * Bs * R * sizeof(float), st) != hipSuccess) return 4;
     const int64_t sdk = L1 * Bs * G5, sxk = L1 * Bs * E;
+    // (every cell's dS_i = dS + i Bs 5R is aligned as dS is, so the choice below is one for the run)
+    const bool bwd_fused = E == R && E == 128 && !env_on("NICNES_SENS_TILE_BWD") &&
+                           bsq_fits(sa(w->dS, sdk, G5, 1), Bs, G5, Wi, E, E) && al(Wh);
     for (int i = L; i >= 0; --i) {
         float* dSi = w->dS + (int64_t)i * Bs * G5;
         hipLaunchKernelGGL(sens_cell_bwd, dim3(blocks((int64_t)K * Bs * R, 256)), dim3(256), 0, st, w->dH, w->dC, Ss(i),
@@ -1227,16 +1237,15 @@ extern "C" int nicnes_sens_run(SensWork* w, const SensParams* p, hipStream_t st)
         // dX_i = dS_i Wi ([5R, E] row-major), dH_{i-1} = dS_i Wh: one launch of both (Wi, Wh stay put over k), 2 seeds
         // per workgroup (4 x (1 or 2) x 32 workgroups at Bs = 128, K = 95); the tile kernel with NICNES_SENS_TILE_BWD
         // (the fused launch puts dH's columns at the second 128-column tile: E == R == 128 exactly)
-        if (E == R && E == 128 && !env_on("NICNES_SENS_TILE_BWD") && bsq_fits(sa(dSi, sdk, G5, 1), Bs, G5, Wi, E, E) &&
-            al(Wh)) {
+        if (bwd_fused) {
             const int kb2 = 2, nzb = (K + kb2 - 1) / kb2;
             hipLaunchKernelGGL((sens_bsq<false, 2>), dim3(blocks(Bs, 32), i >= 1 ? 2 : 1, nzb), dim3(256), 0, st,
                                sa(dSi, sdk, G5, 1), Wi, Wh, (int64_t)E, Bs, E, i >= 1 ? 2 * E : E, G5, K, kb2,
                                w->dX + (int64_t)i * Bs * E, w->dH, sxk, (int64_t)Bs * R, (int64_t)E);
         } else {
-            gemm(sa(dSi, sdk, G5, 1), targs(Bs, E, G5, Wi, 0, E, 1, w->dX + (int64_t)i * Bs * E, sxk, E, 1), K, st);
+            gemm(w, sa(dSi, sdk, G5, 1), targs(Bs, E, G5, Wi, 0, E, 1, w->dX + (int64_t)i * Bs * E, sxk, E, 1), K, st);
             if (i >= 1)
-                gemm(sa(dSi, sdk, G5, 1), targs(Bs, R, G5, Wh, 0, R, 1, w->dH, (int64_t)Bs * R, R, 1), K, st);
+                gemm(w, sa(dSi, sdk, G5, 1), targs(Bs, R, G5, Wh, 0, R, 1, w->dH, (int64_t)Bs * R, R, 1), K, st);
         }
     }
     // gate weights: G_k[g, e] = sum over (cell i, b) of dS_k[i, b, g] X_i[b, e] (h2h: cells 1..L with H_{i-1})
@@ -1300,5 +1309,16 @@ extern "C" int nicnes_sens_run(SensWork* w, const SensParams* p, hipStream_t st)
     for (int q = 0; q < 9; ++q) sg.nz[q] = nz[q];
     hipLaunchKernelGGL(sens_finish, dim3(blocks(D, 256)), dim3(256), 0, st, part, D, sg, 1.f / (float)Bs, p->underflow,
                        p->out);
-    return hipGetLastError() == hipSuccess ? 0 : 6;
+    if (hipGetLastError() != hipSuccess) return 6;
+    w->paths = (lsq_used ? SENS_PATH_LOGIT_FAST : 0) | (bwd_fused ? SENS_PATH_BWD_FUSED : 0) |
+               (bsq ? SENS_PATH_GATES_BSQ : 0) | (emb1 ? SENS_PATH_EMB_TWO_PASS : 0);
+    return 0;
+}
+
+extern "C" int nicnes_sens_last_paths(const SensWork* w, int32_t out[3]) {
+    if (!w || !out || w->paths < 0) return 1;
+    out[0] = w->paths;
+    out[1] = w->gemm_v4;
+    out[2] = w->gemm_scalar;
+    return 0;
 }

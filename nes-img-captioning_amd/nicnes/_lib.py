@@ -21,7 +21,7 @@ EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_param_offsets_l
            'nicnes_comm_attach', 'nicnes_comm_destroy', 'nicnes_comm_count', 'nicnes_clear_faults', 'nicnes_allgather_fitness', 'nicnes_allreduce_grad',
            'nicnes_noise_vectors', 'nicnes_set_batches', 'nicnes_evaluate_batches', 'nicnes_set_mutation',
            'nicnes_set_mutation_proportional', 'nicnes_theta_zeros',
-           'nicnes_set_decode_coop', 'nicnes_decode_path', 'nicnes_sum_sensitivity', 'nicnes_grad_partial_range',
+           'nicnes_set_decode_coop', 'nicnes_decode_path', 'nicnes_sum_sensitivity', 'nicnes_sens_paths', 'nicnes_grad_partial_range',
            'nicnes_evaluate_theta', 'nicnes_set_sample_draws', 'nicnes_set_rows_per_image',
            'nicnes_last_decode_lse', 'nicnes_test_logit_chain', 'nicnes_test_score_rows',
            'nicnes_test_certify_items', 'nicnes_test_certify_items_owned',
@@ -121,6 +121,7 @@ def lib(path=None):
         'nicnes_test_certify_items_owned': (c.c_int, [vp, u64, i32, f32, i32, i32, vp, vp, i32, vp, vp]),
         'nicnes_test_score_rows': (c.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
         'nicnes_sum_sensitivity': (c.c_int, [vp, i32, f32, vp, vp]),
+        'nicnes_sens_paths': (c.c_int, [vp, vp]),
         'nicnes_split_create': (c.c_int, [vp, vp, i32, vp, i32, vp, vp, vp, i64, f64, c.POINTER(vp), vp]),
         'nicnes_split_destroy': (c.c_int, [vp, vp]),
         'nicnes_split_decode': (c.c_int, [vp, vp, i32, i32, vp, vp, vp]),

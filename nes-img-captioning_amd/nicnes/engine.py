@@ -463,6 +463,19 @@ class Engine:
                   self.h, 'sum_sensitivity')
         return v
 
+    SENS_PATH_BITS = ('logit_fast', 'bwd_fused', 'gates_bsq', 'emb_two_pass')
+
+    def sens_paths(self):
+        """The kernels the last sensitivity run of this handle chose (sum_sensitivity, or es_sensitivity's last slot):
+        {'logit_fast', 'bwd_fused', 'gates_bsq', 'emb_two_pass': bool (False: the general tile / range kernel),
+        'gemm_v4', 'gemm_scalar': the run's tile products with 16-byte and with scalar operand loads}. Host
+        bookkeeping (nicnes_sens_paths): no kernel runs. Raises before the first run."""
+        out = (ctypes.c_int32 * 3)()
+        check(self.L.nicnes_sens_paths(self.h, out), self.h, 'sens_paths')
+        d = {name: bool(out[0] >> i & 1) for i, name in enumerate(self.SENS_PATH_BITS)}
+        d.update(gemm_v4=int(out[1]), gemm_scalar=int(out[2]))
+        return d
+
     def set_decode_coop(self, mode=1):
         """1 (default): the split shape (128-row slabs, S = 2 or 4, every workgroup resident) runs as one
         persistent launch whose workgroups hand partial states and h' to each other; 0: two launches per
