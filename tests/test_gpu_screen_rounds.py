@@ -7,6 +7,9 @@ loop on the waves that hold a bad row only.
 
 Inputs (P = 2, sigma = 0, theta = make_theta(dims, 0, 4.0, 0.1), both signs and members decode the same tokens).
 Lane (row, half 0) owns ids 64 s + 32 c + 8 g + e (c < 2, g < 4, e < 4) of stage s, in pairs (e = 0, 1), (e = 2, 3).
+Every id planted here lies in lane half 0, tile c = 0, group g = 0, pair 0 or 1, and tied ids share one logit row, so the
+screen keeps their order; lane half 1, tile 1, pairs 2 .. 15 and ids the screen misorders are the worlds of
+tests/screen_worlds.py (tests/test_gpu_screen_misorder.py).
   tied K          K ids 64 (2 j + 1), j < K, one per stage, share one logit row; b = 30 - j 2^-12. The span is below
                   2 eps (eps >= 2^-13 30) and far above the tie window (2^-24 at lse < 2), and chains of identical
                   products started a multiple of ulp(30) apart stay that far apart: every tied id is a candidate of
