@@ -171,7 +171,36 @@ int nicnes_theta_zeros(nicnes_handle* h, int64_t* count_out_host, void* stream);
 #define NICNES_FITNESS_SAMPLE 5           /* 'sample' */
 #define NICNES_FITNESS_SELF_CRITICAL 6    /* 'self_critical' */
 #define NICNES_FITNESS_SC_LOSS 7          /* 'sc_loss': LogFitnessCriterion */
+/* XENT (an extension: the reference's Fitness enum has no such member, its xent models come from upstream training):
+ * the teacher-forced likelihood of the batch's label rows, the reference rows [n_refs, seq_length] of
+ * nicnes_set_batch(es), each under its own image. The definition is self-critical.pytorch's FCModel._forward +
+ * LanguageModelCriterion (misc/utils.py) over the reference's modules: the image step as FCModel._sample runs it at
+ * t = 0 (its logits discarded); then for s = 0..T (T = seq_length, w[T] := 0) the cell over embed(u_s), u_0 = 0 (BOS),
+ * u_s = w[s - 1], and lp_s = fl32(fl32(x[w[s]] - m) - lse) with the greedy decode's exact exp-sum. Target s counts
+ * when s = 0 or w[s - 1] > 0 (the words plus one end token: 1..T + 1 targets per row). Per row n_tok = the counted
+ * targets and lp_sum = the fp64 sum of their lp_s in step order; over rows loss = -sum lp_sum / sum n_tok (the
+ * criterion's per-token mean), both sums in a fixed order in fp64 without floating atomics; the fitness of a candidate
+ * is -loss over the label rows of its batch (higher is better). In this mode nicnes_evaluate / _lp / _batches return
+ * that fitness for both signs of every member (seq_out and logprob_out must be NULL: nothing is decoded) and
+ * nicnes_evaluate_theta returns it for theta. E = R = 128 models only: wide and layer_n handles, a mutation set by
+ * nicnes_set_mutation* and nicnes_es_evaluate are NICNES_ERR_UNSUPPORTED with this mode, before anything is enqueued. */
+#define NICNES_FITNESS_XENT 8
 int nicnes_set_fitness_mode(nicnes_handle* h, int32_t mode);
+/* After an evaluate in XENT mode: candidate cand's (member k sign s: 2 k + s; nicnes_evaluate_theta: 0) per-row
+ * lp_sum_out [rows] fp64 and n_tok_out [rows] int32 (either nullable; host or device pointers, copied on the stream),
+ * rows = the label rows of the candidate's batch (nicnes_xent_batch_rows). NICNES_ERR_INVALID without such an evaluate,
+ * or with cand or rows outside it. */
+int nicnes_xent_rows(nicnes_handle* h, int32_t cand, int32_t rows, double* lp_sum_out, int32_t* n_tok_out, void* stream);
+/* rows_out_host[0] = the label rows of batch `batch` of the batches held. */
+int nicnes_xent_batch_rows(nicnes_handle* h, int32_t batch, int32_t* rows_out_host);
+/* Test entry, in the style of nicnes_test_score_rows: the XENT evaluate of members member_begin .. + count (theta_batch
+ * < 0; member_batch_host as nicnes_evaluate_batches) or of theta itself on batch theta_batch (>= 0; count ignored),
+ * returning every counted target's lp_s and 0 elsewhere: lp_out_dev [count, 2, stride, seq_length + 1] fp32 with
+ * stride = the largest batch's label rows, or [rows of the batch, seq_length + 1] for theta. fitness_out_dev: [count, 2]
+ * or [1]. */
+int nicnes_test_xent_steps(nicnes_handle* h, uint64_t iteration, int32_t member_begin, int32_t count, float sigma,
+                           const int32_t* member_batch_host, int32_t theta_batch, double* fitness_out_dev,
+                           float* lp_out_dev, void* stream);
 
 /* Rows per image of the sampled modes: each image of the batch is decoded n times (the reference's
  * seq_per_img copies, dataloader.py:175, which it samples independently), row r reading image r / n and
@@ -255,6 +284,16 @@ int nicnes_split_score(nicnes_handle* h, nicnes_split* split, int32_t first, int
 /* nicnes_split_decode + nicnes_split_score of its tokens; seq_out (nullable) [count, seq_length] receives them. */
 int nicnes_split_evaluate(nicnes_handle* h, nicnes_split* split, int32_t first, int32_t count, int64_t* totals_out_dev,
                           double* metrics_out_dev, double* row_cider_out_dev, int32_t* seq_out, void* stream);
+
+/* The teacher-forced cross-entropy (NICNES_FITNESS_XENT's definition) of the handle's current theta on the label rows
+ * (the split's reference rows) of images [first, first + count), in ONE enqueue; no handle state is read but theta or
+ * changed (the fitness mode, df table, batches and mutation stay as they are). out2_dev [2] fp64 = loss, perplexity
+ * exp(loss); tokens_out_dev [1] int64 = sum n_tok; lp_sum_out_dev / n_tok_out_dev (nullable) [rows] = the range's
+ * rows img_ref_start[first] .. img_ref_start[first + count). The same bits on every run, and those of
+ * nicnes_evaluate_theta in XENT mode on a batch of the same images. NICNES_ERR_UNSUPPORTED on a decode-only split and
+ * on wide / layer_n handles. */
+int nicnes_split_xent(nicnes_handle* h, nicnes_split* split, int32_t first, int32_t count, double* out2_dev,
+                      int64_t* tokens_out_dev, double* lp_sum_out_dev, int32_t* n_tok_out_dev, void* stream);
 
 /* Beam-search decode of the handle's current theta on images [first, first + count) of the split, for evaluation, in
  * ONE enqueue with no host synchronisation (the work buffers grow with the largest (count, beam) seen, synchronising

@@ -203,5 +203,30 @@ extern "C" hipError_t nicnes_launch_decode_wide(const DecodeParams* p, int E, in
 extern "C" hipError_t nicnes_launch_test_ln_cell(const DecodeParams* p, int E, int R, const int64_t* tail6,
                                                  const float* xin, const float* hin, const float* cin, int rows,
                                                  float* hout, float* cout, hipStream_t stream);
+// the teacher-forced forward (xent_kernels.hip): log-probs of label rows under theta +- delta, E = R = 128 only
+struct XentArgs {
+    const int32_t* labels;         // [rows held, T] label rows: word ids, 0-padded
+    const int32_t* row_img;        // [rows held] the image (row of p.fc) of each label row, ascending
+    const int32_t* img_ref_start;  // batches: [images + 1] (the batch's rows: start[k B_img] .. start[(k + 1) B_img]); or NULL
+    double* lp_sum;                // out: batches [members, 2, max_rows]; flat [row1 - row0]
+    int32_t* n_tok;                // out, likewise
+    float* lp_steps;               // out (nullable), likewise x (T + 1): lp_s of the counted targets (the host zeroes it)
+    int32_t n_img;                 // rows of p.fc
+    int32_t row0, row1;            // the flat range
+    int32_t max_rows;              // batches: the outputs' row stride
+};
+// nicnes_xent_init: per device, once per handle (the kernel's dynamic LDS is above 64 KB)
+extern "C" hipError_t nicnes_xent_init();
+extern "C" size_t nicnes_xent_scratch_floats(int64_t workgroups);
+// row_img[r] = the image whose reference range [img_ref_start[i], img_ref_start[i + 1]) holds row r
+extern "C" hipError_t nicnes_launch_xent_row_map(const int32_t* img_ref_start, int n_img, int32_t* row_img,
+                                                 hipStream_t stream);
+// one launch of members x nslabs workgroups (a flat range: members pseudo-members, nslabs 1), then the n_cand
+// candidates' fitness = sum lp_sum / sum n_tok in a fixed fp64 order (each nullable: fitness, tokens = their sum n_tok,
+// loss2 = {loss, exp(loss)} of candidate 0). Reads theta,
+// noise, noise_idx, fc, member_batch, B_img, scratch (nicnes_xent_scratch_floats(members * nslabs)), F, V1, T, D and
+// the offsets of *p
+extern "C" hipError_t nicnes_launch_xent(const DecodeParams* p, const XentArgs* xa, int members, int nslabs, int n_cand,
+                                         double* fitness, long long* tokens, double* loss2, hipStream_t stream);
 // lane scratch for up to member_count members x row_waves 32-row waves of one sign
 extern "C" size_t nicnes_decode_scratch_floats(int member_count, int row_waves_per_member);

@@ -3788,6 +3788,8 @@ extern "C" hipError_t nicnes_launch_test_logit_chain(const DecodeParams* p, uint
 #include "beam_kernels.hip"
 // the greedy decode of models wider than 128 units and (decode_ln_kernels.hip, #included there) of layer_n models, likewise
 #include "decode_wide_kernels.hip"
+// the teacher-forced forward (the xent fitness, nicnes_split_xent), on the wide frame's helpers, likewise
+#include "xent_kernels.hip"
 
 // ========== test entry: given (row, id) items through the screened decode's certify_tiles ======================
 // One workgroup of the decode's shape. hin [128, 128] is laid out as its eight waves' lane scratch (wave w: sign w >> 2,

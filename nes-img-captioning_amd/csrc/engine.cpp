@@ -31,6 +31,20 @@
 #define MB_RING 4   // pinned staging slots of the member -> batch map (nicnes_evaluate_batches)
 #define DR_RING 4   // pinned staging slots of a draw's image indices and reference starts (nicnes_draw_batches)
 
+// Work of the teacher-forced forward (xent_kernels.hip), grown to the largest launch: lane scratch of `wgs` workgroups,
+// the per-row outputs of `rows` candidate rows, zero slice indices of `pms` pseudo-members (theta itself over a flat
+// range). The handle holds one set (its last XENT evaluate's rows stay readable) and every split its own.
+struct XentWork {
+    float* scratch = nullptr;
+    int64_t wgs = 0;
+    double* lp_sum = nullptr;
+    int32_t* n_tok = nullptr;
+    int64_t rows = 0;
+    uint64_t* zero_idx = nullptr;
+    int32_t pms = 0;
+    double* out = nullptr;            // [4]: fitness | loss, perplexity | sum n_tok (as int64)
+};
+
 struct nicnes_handle {
     nicnes_config cfg;
     int device = 0;
@@ -66,6 +80,13 @@ struct nicnes_handle {
     const int32_t* img_ref_start = nullptr;
     const int32_t* ref_tokens = nullptr;   // the batch's reference rows [n_refs, T] (nicnes_test_batch_state)
     bool batch_set = false;
+    // the xent fitness: label rows = the reference rows held, each under its own image
+    int32_t* x_row_img = nullptr;     // [max_refs] label row -> image (alloc_refs; built whenever a batch is set)
+    std::vector<int32_t> x_row0;      // [n_batches + 1] first label row of every batch held (host)
+    int32_t x_max_rows = 0;           // label rows of the largest batch held
+    XentWork xw;
+    std::vector<int32_t> x_last_rows; // the last XENT evaluate: label rows of every candidate (empty: none yet)
+    int64_t x_last_stride = 0;        // ... and their row stride in xw.lp_sum / n_tok
     // nicnes_draw_batches: the batch buffers a draw gathers into (owned; h->fc, ref_tokens and img_ref_start point at
     // them after a draw), the device copy of the staged words and the pinned ring they travel through. A slot holds
     // [n_img] image indices then [n_img + 1] destination starts, and is reused only after its copy has run (its event)
@@ -251,6 +272,9 @@ struct nicnes_split {
     float* fc = nullptr;              // [N + 2 * SPLIT_ROWS, F]: the tail rows (zeros) are decoded and dropped
     int32_t* ref_tokens = nullptr;    // [n_refs, T]
     int32_t* img_ref_start = nullptr; // [N + 1]
+    std::vector<int32_t> start_host;  // ... its host copy (nicnes_split_xent sizes its launch from it)
+    int32_t* row_img = nullptr;       // [n_refs] label row -> image (nicnes_split_xent)
+    XentWork xw;
     uint64_t* hash_keys = nullptr;    // the split's df table
     double* hash_vals = nullptr;
     uint64_t hash_mask = 0;
@@ -479,16 +503,18 @@ void ensure_screen(nicnes_handle* h) {
 }
 
 int alloc_refs(nicnes_handle* h, int max_refs) {
-    void* old[] = {h->ref_keys, h->ref_vec, h->ref_count, h->ref_len2, h->ref_norm};
+    void* old[] = {h->ref_keys, h->ref_vec, h->ref_count, h->ref_len2, h->ref_norm, h->x_row_img};
     for (void* q : old)
         if (q) (void)hipFree(q);
     h->ref_keys = nullptr; h->ref_vec = nullptr; h->ref_count = nullptr; h->ref_len2 = nullptr; h->ref_norm = nullptr;
+    h->x_row_img = nullptr;
     const size_t MR = (size_t)max_refs;
     int rc = dalloc(h, &h->ref_keys, MR * 64);
     if (!rc) rc = dalloc(h, &h->ref_vec, MR * 64);
     if (!rc) rc = dalloc(h, &h->ref_count, MR);
     if (!rc) rc = dalloc(h, &h->ref_len2, MR);
     if (!rc) rc = dalloc(h, &h->ref_norm, MR * 4);
+    if (!rc) rc = dalloc(h, &h->x_row_img, MR);
     if (!rc) h->cfg.max_refs = max_refs;
     return rc;
 }
@@ -536,6 +562,64 @@ int alloc_images(nicnes_handle* h, int n_img) {
     if (!rc) rc = dalloc(h, &h->img_vr, N * IMG_ROWS * IMG_MAXR);
     if (!rc) h->img_cap = n_img;
     return rc;
+}
+
+void xent_work_free(XentWork* w) {
+    void* bufs[] = {w->scratch, w->lp_sum, w->n_tok, w->zero_idx, w->out};
+    for (void* q : bufs)
+        if (q) (void)hipFree(q);
+    *w = XentWork();
+}
+
+// grown outside every launch (synchronising then)
+int xent_work_grow(nicnes_handle* h, XentWork* w, int64_t wgs, int64_t rows, int32_t pms) {
+    if (!w->out) {
+        int rc = dalloc(h, &w->out, 4);
+        if (rc) return rc;
+    }
+    if (wgs > w->wgs) {
+        HIPC(h, hipDeviceSynchronize());
+        if (w->scratch) (void)hipFree(w->scratch);
+        w->scratch = nullptr;
+        w->wgs = 0;
+        int rc = dalloc(h, &w->scratch, nicnes_xent_scratch_floats(wgs));
+        if (rc) return rc;
+        w->wgs = wgs;
+    }
+    if (rows > w->rows) {
+        HIPC(h, hipDeviceSynchronize());
+        if (w->lp_sum) (void)hipFree(w->lp_sum);
+        if (w->n_tok) (void)hipFree(w->n_tok);
+        w->lp_sum = nullptr; w->n_tok = nullptr;
+        w->rows = 0;
+        int rc = dalloc(h, &w->lp_sum, (size_t)rows);
+        if (!rc) rc = dalloc(h, &w->n_tok, (size_t)rows);
+        if (rc) return rc;
+        w->rows = rows;
+    }
+    if (pms > w->pms) {
+        HIPC(h, hipDeviceSynchronize());
+        if (w->zero_idx) (void)hipFree(w->zero_idx);
+        w->zero_idx = nullptr;
+        w->pms = 0;
+        int rc = dalloc(h, &w->zero_idx, (size_t)pms);
+        if (rc) return rc;
+        HIPC(h, hipMemset(w->zero_idx, 0, (size_t)pms * sizeof(uint64_t)));
+        w->pms = pms;
+    }
+    return NICNES_OK;
+}
+
+// the batches' label rows for the xent fitness, from the host's copy st [n_img + 1] of img_ref_start: every batch's first
+// row, the largest batch, and (enqueued) the row -> image map
+int xent_batch_rows(nicnes_handle* h, const int32_t* st, int n_batches, int B, hipStream_t s) {
+    h->x_row0.resize((size_t)n_batches + 1);
+    h->x_max_rows = 0;
+    for (int k = 0; k <= n_batches; ++k) h->x_row0[(size_t)k] = st[(size_t)k * B];
+    for (int k = 0; k < n_batches; ++k) h->x_max_rows = std::max(h->x_max_rows, h->x_row0[k + 1] - h->x_row0[k]);
+    h->x_last_rows.clear();
+    HIPC(h, nicnes_launch_xent_row_map(h->img_ref_start, n_batches * B, h->x_row_img, s));
+    return NICNES_OK;
 }
 
 }  // namespace
@@ -648,6 +732,7 @@ int nicnes_create(const nicnes_config* cfg, int device, nicnes_handle** out) {
     }
     if (!rc && nicnes_decode_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_init");
     if (!rc && nicnes_decode_wide_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_wide_init");
+    if (!rc && nicnes_xent_init() != hipSuccess) rc = fail(h, NICNES_ERR_HIP, "nicnes_xent_init");
     if (!rc && (nicnes_decode_occupancy(&h->coop_occ, &h->sample_occ) != hipSuccess || h->coop_occ < 1 ||
                 h->sample_occ < 1))
         rc = fail(h, NICNES_ERR_HIP, "nicnes_decode_occupancy");
@@ -707,7 +792,9 @@ int nicnes_destroy(nicnes_handle* h) {
                     h->hash_keys, h->hash_vals, h->img_hkey, h->img_hrow, h->img_vr, h->alive, h->part,
                     h->rank_key, h->rank_idx, h->mbatch, h->mut_vec, h->dbuf, h->didx, h->noise_sc, h->coop_ctr,
                     h->zero_noise, h->zero_idx, h->sens_tok, h->su, h->base_scores, h->slog, h->slog_slots, h->zcount,
-                    h->screen_cap, h->screen_norm, h->screen_ctr, h->queue_ring, h->queue_ctl, h->dr_fc, h->dr_refs, h->dr_start, h->dr_stage};
+                    h->screen_cap, h->screen_norm, h->screen_ctr, h->queue_ring, h->queue_ctl, h->dr_fc, h->dr_refs, h->dr_start, h->dr_stage,
+                    h->x_row_img};
+    xent_work_free(&h->xw);
     if (h->sens) nicnes_sens_destroy(h->sens);
     for (void* p : bufs)
         if (p) (void)hipFree(p);
@@ -895,6 +982,10 @@ int nicnes_set_batches(nicnes_handle* h, const float* fc, int32_t n_batches, int
     h->n_refs = n_refs;
     h->img_ref_start = img_ref_start;
     h->ref_tokens = ref_tokens;
+    if (int rc = xent_batch_rows(h, st.data(), n_batches, B, (hipStream_t)stream)) {
+        h->batch_set = false;
+        return rc;
+    }
     CiderTables tb = tables_of(h);
     HIPC(h, nicnes_launch_cook_refs(ref_tokens, n_refs, h->cfg.seq_length, &tb, (hipStream_t)stream));
     // per-image n-gram tables when every image has at most IMG_MAXR references (else the
@@ -1110,6 +1201,7 @@ int nicnes_draw_batches(nicnes_handle* h, nicnes_trainset* ts, const int32_t* im
     h->n_refs = n_refs;
     h->img_ref_start = h->dr_start;
     h->ref_tokens = h->dr_refs;
+    if (int rc = xent_batch_rows(h, dst, n_batches, B, s)) return rc;
     CiderTables tb = tables_of(h);
     HIPC(h, nicnes_launch_cook_refs(h->dr_refs, n_refs, h->cfg.seq_length, &tb, s));
     h->img_tables = maxr <= IMG_MAXR;
@@ -1224,9 +1316,11 @@ int nicnes_set_sample_draws(nicnes_handle* h, const double* u_host, int64_t n) {
 
 int nicnes_set_fitness_mode(nicnes_handle* h, int32_t mode) {
     if (!h) return NICNES_ERR_INVALID;
-    if (mode < NICNES_FITNESS_GREEDY || mode > NICNES_FITNESS_SC_LOSS)
+    if (mode < NICNES_FITNESS_GREEDY || mode > NICNES_FITNESS_XENT)
         return fail(h, NICNES_ERR_UNSUPPORTED, "fitness mode: the engine implements greedy, greedy_{log,exp,lin,avg}prob, "
-                                               "sample, self_critical and sc_loss");
+                                               "sample, self_critical, sc_loss and xent");
+    if (h->wide && mode == NICNES_FITNESS_XENT)
+        return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "the xent fitness is not supported (E = R = 128 only)");
     if (h->wide && mode >= NICNES_FITNESS_SAMPLE)
         return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "the sampled fitness "
                                                "modes are not supported (greedy, greedy_*)");
@@ -1507,6 +1601,90 @@ static int decode_and_score(nicnes_handle* h, const DecodeParams& p, const MutHe
     return NICNES_OK;
 }
 
+// The teacher-forced forward of theta over the label rows [row0, row1) of (labels, row_img, fc [n_img, F]) as one flat
+// range of pseudo-members over the zero noise slice: per-row results in w->lp_sum / n_tok, the sums in w->out.
+static int xent_flat(nicnes_handle* h, XentWork* w, const int32_t* labels, const int32_t* row_img, const float* fc,
+                     int32_t n_img, int32_t row0, int32_t row1, float* steps_out, hipStream_t s) {
+    const int rows = row1 - row0, n_pm = (rows + 255) / 256;
+    if (rows < 1) return fail(h, NICNES_ERR_INVALID, "xent: no label rows in the range");
+    if (int rc = ensure_zero_noise(h)) return rc;
+    if (int rc = xent_work_grow(h, w, n_pm, (int64_t)n_pm * 256, n_pm)) return rc;
+    DecodeParams p = decode_base(h);
+    p.theta = h->theta32;
+    p.noise = h->zero_noise;
+    p.noise_idx = w->zero_idx;
+    p.fc = fc;
+    p.scratch = w->scratch;
+    const XentArgs xa{labels, row_img, nullptr, w->lp_sum, w->n_tok, steps_out, n_img, row0, row1, 0};
+    if (steps_out) HIPC(h, hipMemsetAsync(steps_out, 0, (size_t)rows * (h->cfg.seq_length + 1) * sizeof(float), s));
+    HIPC(h, nicnes_launch_xent(&p, &xa, n_pm, 1, 1, w->out, (long long*)(w->out + 3), w->out + 1, s));
+    return NICNES_OK;
+}
+
+// NICNES_FITNESS_XENT: the evaluate of members member_begin .. + count on their batches' label rows (theta_batch < 0),
+// or of theta itself on the rows of batch theta_batch. steps_out (nullable): nicnes_test_xent_steps.
+static int xent_evaluate(nicnes_handle* h, uint64_t iteration, int32_t member_begin, int32_t count, float sigma,
+                         const int32_t* member_batch_host, int theta_batch, double* fitness_out, float* steps_out,
+                         hipStream_t s) {
+    const bool theta = theta_batch >= 0;
+    if (h->wide) return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "the xent fitness is not supported (E = R = 128 only)");
+    if (h->mut_mode)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "xent fitness: safe and proportional mutations are not supported (plain only)");
+    if (!theta && (count < 1 || count > h->cfg.max_members)) return fail(h, NICNES_ERR_INVALID, "count out of [1, max_members]");
+    if (!theta && !h->noise) return fail(h, NICNES_ERR_INVALID, "nicnes_set_noise_table first");
+    if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
+    if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
+    if (theta && theta_batch >= h->n_batches) return fail(h, NICNES_ERR_INVALID, "batch outside [0, n_batches)");
+    HIPC(h, hipSetDevice(h->device));
+    if (h->timing) HIPC(h, hipEventRecord(h->ev[0], s));
+    h->n_dev = 0;
+    h->multi_stream = false;
+    if (theta) {
+        const int32_t r0 = h->x_row0[(size_t)theta_batch], r1 = h->x_row0[(size_t)theta_batch + 1];
+        h->x_last_rows.clear();
+        if (int rc = xent_flat(h, &h->xw, h->ref_tokens, h->x_row_img, h->fc, h->n_img, r0, r1, steps_out, s)) return rc;
+        HIPC(h, hipMemcpyAsync(fitness_out, h->xw.out, sizeof(double), hipMemcpyDefault, s));
+        h->x_last_rows.assign(1, r1 - r0);
+        h->x_last_stride = r1 - r0;
+    } else {
+        const int32_t* mb = nullptr;
+        if (int rc = stage_member_batch(h, member_batch_host, count, s, &mb)) return rc;
+        std::vector<int32_t> rows((size_t)2 * count);
+        int most = 0;
+        for (int k = 0; k < count; ++k) {
+            const int bk = member_batch_host ? member_batch_host[k] : 0;
+            rows[2 * k] = rows[2 * k + 1] = h->x_row0[(size_t)bk + 1] - h->x_row0[(size_t)bk];
+            most = std::max(most, rows[2 * k]);
+        }
+        const int nslabs = (most + 127) / 128, stride = h->x_max_rows;
+        h->x_last_rows.clear();
+        if (int rc = xent_work_grow(h, &h->xw, (int64_t)count * nslabs, (int64_t)2 * count * stride, 0)) return rc;
+        HIPC(h, nicnes_launch_noise_index(h->cfg.noise_seed, iteration, (uint64_t)member_begin, count, h->cfg.noise_len,
+                                          (uint64_t)h->D, h->nidx, s));
+        if (int rc = ensure_noise_scaled(h, sigma, s)) return rc;
+        DecodeParams p = decode_base(h);
+        p.theta = h->theta32;
+        p.noise = h->noise_sc;
+        p.noise_idx = h->nidx;
+        p.fc = h->fc;
+        p.member_batch = mb;
+        p.B_img = h->B;
+        p.scratch = h->xw.scratch;
+        const XentArgs xa{h->ref_tokens, h->x_row_img, h->img_ref_start, h->xw.lp_sum, h->xw.n_tok, steps_out, h->n_img,
+                          0, 0, stride};
+        if (steps_out)
+            HIPC(h, hipMemsetAsync(steps_out, 0, (size_t)2 * count * stride * (h->cfg.seq_length + 1) * sizeof(float), s));
+        HIPC(h, nicnes_launch_xent(&p, &xa, count, nslabs, 2 * count, fitness_out, nullptr, nullptr, s));
+        h->x_last_rows = rows;
+        h->x_last_stride = stride;
+    }
+    if (h->timing) {
+        HIPC(h, hipEventRecord(h->ev[1], s));
+        HIPC(h, hipEventRecord(h->ev[2], s));
+    }
+    return NICNES_OK;
+}
+
 // eval_theta: the sigma = 0 rollout of theta itself (count 1), decoded ONCE: sign + takes the first half of the
 // batch's images and sign - the second (at sigma = 0 both signs are theta, so the halves are one decode of the
 // batch), scored as one rollout of B rows
@@ -1516,6 +1694,13 @@ static int evaluate_impl(nicnes_handle* h, uint64_t iteration, int32_t member_be
                          void* stream, bool eval_theta, double* scores_out = nullptr) {
     if (!h || !fitness_out || member_begin < 0) return NICNES_ERR_INVALID;
     const int mode = h->fitness_mode;
+    if (mode == NICNES_FITNESS_XENT) {
+        if (seq_out || logprob_out)
+            return fail(h, NICNES_ERR_INVALID, "xent fitness: nothing is decoded (seq_out and logprob_out must be NULL)");
+        const int tb = !eval_theta ? -1 : (member_batch_host ? member_batch_host[0] : 0);
+        return xent_evaluate(h, iteration, member_begin, count, sigma, member_batch_host, tb, fitness_out, nullptr,
+                             (hipStream_t)stream);
+    }
     const bool sampled = mode >= NICNES_FITNESS_SAMPLE;
     const bool self_critical = mode == NICNES_FITNESS_SELF_CRITICAL || mode == NICNES_FITNESS_SC_LOSS;
     if (self_critical && !scores_out) {
@@ -1694,14 +1879,45 @@ int nicnes_evaluate_theta(nicnes_handle* h, int32_t batch, uint64_t iteration, d
                          stream, true);
 }
 
+int nicnes_xent_rows(nicnes_handle* h, int32_t cand, int32_t rows, double* lp_sum_out, int32_t* n_tok_out, void* stream) {
+    if (!h) return NICNES_ERR_INVALID;
+    if (h->x_last_rows.empty()) return fail(h, NICNES_ERR_INVALID, "no xent evaluate to read rows of");
+    if (cand < 0 || (size_t)cand >= h->x_last_rows.size() || rows < 0 || rows > h->x_last_rows[(size_t)cand])
+        return fail(h, NICNES_ERR_INVALID, "candidate or rows outside the last xent evaluate");
+    HIPC(h, hipSetDevice(h->device));
+    const size_t o = (size_t)cand * (size_t)h->x_last_stride;
+    if (lp_sum_out)
+        HIPC(h, hipMemcpyAsync(lp_sum_out, h->xw.lp_sum + o, (size_t)rows * sizeof(double), hipMemcpyDefault, (hipStream_t)stream));
+    if (n_tok_out)
+        HIPC(h, hipMemcpyAsync(n_tok_out, h->xw.n_tok + o, (size_t)rows * sizeof(int32_t), hipMemcpyDefault, (hipStream_t)stream));
+    return NICNES_OK;
+}
+
+int nicnes_xent_batch_rows(nicnes_handle* h, int32_t batch, int32_t* rows_out_host) {
+    if (!h || !rows_out_host) return NICNES_ERR_INVALID;
+    if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
+    if (batch < 0 || batch >= h->n_batches) return fail(h, NICNES_ERR_INVALID, "batch outside [0, n_batches)");
+    rows_out_host[0] = h->x_row0[(size_t)batch + 1] - h->x_row0[(size_t)batch];
+    return NICNES_OK;
+}
+
+int nicnes_test_xent_steps(nicnes_handle* h, uint64_t iteration, int32_t member_begin, int32_t count, float sigma,
+                           const int32_t* member_batch_host, int32_t theta_batch, double* fitness_out_dev,
+                           float* lp_out_dev, void* stream) {
+    if (!h || !fitness_out_dev || !lp_out_dev || member_begin < 0) return NICNES_ERR_INVALID;
+    return xent_evaluate(h, iteration, member_begin, count, sigma, member_batch_host, theta_batch, fitness_out_dev,
+                         lp_out_dev, (hipStream_t)stream);
+}
+
 // ---- resident evaluation splits ---------------------------------------------------------------------------------
 static void split_free(nicnes_split* sp) {
     void* bufs[] = {sp->fc, sp->ref_tokens, sp->img_ref_start, sp->hash_keys, sp->hash_vals, sp->ref_keys, sp->ref_vec,
                     sp->ref_count, sp->ref_len2, sp->ref_norm, sp->img_stats, sp->img_rouge, sp->img_cider, sp->seq, sp->lp,
                     sp->scratch, sp->alive, sp->coop_ctr, sp->zero_idx, sp->block, sp->part, sp->beam_seq, sp->beam_score,
-                    sp->beam_xscr};
+                    sp->beam_xscr, sp->row_img};
     for (void* q : bufs)
         if (q) (void)hipFree(q);
+    xent_work_free(&sp->xw);
     delete sp;
 }
 
@@ -1779,6 +1995,10 @@ int nicnes_split_create(nicnes_handle* h, const float* fc, int32_t N, const int3
         if (rc) return rc;
         HIPC(h, hipMemcpy(sp->ref_tokens, ref_tokens, NR * T * sizeof(int32_t), hipMemcpyDefault));
         HIPC(h, hipMemcpy(sp->img_ref_start, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        sp->start_host = st;
+        rc = dalloc(h, &sp->row_img, NR);
+        if (rc) return rc;
+        HIPC(h, nicnes_launch_xent_row_map(sp->img_ref_start, N, sp->row_img, s));
         HIPC(h, hipMemset(sp->hash_keys, 0, cap * sizeof(uint64_t)));
         sp->hash_mask = cap - 1;
         if (n_df > 0) {
@@ -1969,6 +2189,29 @@ int nicnes_split_evaluate(nicnes_handle* h, nicnes_split* sp, int32_t first, int
     if (int rc = split_decode_impl(h, sp, first, count, seq_out, nullptr, (hipStream_t)stream, &seq)) return rc;
     return split_score_impl(h, sp, first, count, seq, totals_out_dev, metrics_out_dev, row_cider_out_dev,
                             (hipStream_t)stream);
+}
+
+int nicnes_split_xent(nicnes_handle* h, nicnes_split* sp, int32_t first, int32_t count, double* out2_dev,
+                      int64_t* tokens_out_dev, double* lp_sum_out_dev, int32_t* n_tok_out_dev, void* stream) {
+    if (!h || !sp || !out2_dev) return NICNES_ERR_INVALID;
+    if (!split_of(h, sp)) return fail(h, NICNES_ERR_INVALID, "not a split of this handle");
+    if (h->wide) return fail(h, NICNES_ERR_UNSUPPORTED, wide_what(h) + "the xent loss is not supported (E = R = 128 only)");
+    if (sp->n_refs == 0) return fail(h, NICNES_ERR_UNSUPPORTED, "a decode-only split has no label rows for the xent loss");
+    if (first < 0 || count < 1 || (int64_t)first + count > sp->N)
+        return fail(h, NICNES_ERR_INVALID, "range outside the split's images");
+    if (!h->theta_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_theta first");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(h, hipSetDevice(h->device));
+    const int32_t r0 = sp->start_host[(size_t)first], r1 = sp->start_host[(size_t)first + count];
+    if (int rc = xent_flat(h, &sp->xw, sp->ref_tokens, sp->row_img, sp->fc, sp->N, r0, r1, nullptr, s)) return rc;
+    const size_t rows = (size_t)(r1 - r0);
+    HIPC(h, hipMemcpyAsync(out2_dev, sp->xw.out + 1, 2 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (tokens_out_dev) HIPC(h, hipMemcpyAsync(tokens_out_dev, sp->xw.out + 3, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (lp_sum_out_dev)
+        HIPC(h, hipMemcpyAsync(lp_sum_out_dev, sp->xw.lp_sum, rows * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (n_tok_out_dev)
+        HIPC(h, hipMemcpyAsync(n_tok_out_dev, sp->xw.n_tok, rows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return NICNES_OK;
 }
 
 // ---- beam-search decode of a split (evaluation only; beam_kernels.hip) ------------------------------------------------
@@ -2569,6 +2812,8 @@ int nicnes_test_score_rows(nicnes_handle* h, const int32_t* seq, int32_t n_cand,
                            double* fitness_out, void* stream) {
     if (!h || !seq || !scores_out || !fitness_out) return NICNES_ERR_INVALID;
     if (!h->batch_set) return fail(h, NICNES_ERR_INVALID, "nicnes_set_batch first");
+    if (h->fitness_mode == NICNES_FITNESS_XENT)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "nicnes_test_score_rows: the xent fitness scores no token rows");
     const int rpi = h->fitness_mode >= NICNES_FITNESS_SAMPLE ? h->rpi : 1;
     if (rows != h->B * rpi) return fail(h, NICNES_ERR_INVALID, "rows must be B * rows_per_image (B in the greedy modes)");
     // h->row_scores holds [2 * max_members, rows] and h->mbatch [max_members] (the evaluate's 2 * count candidates)
@@ -3171,6 +3416,8 @@ int nicnes_es_evaluate(nicnes_handle* h, uint64_t generation, int32_t pair_begin
     ES_STATE(h);
     if (!fitness_out || !parent_of_host || pair_begin < 0) return NICNES_ERR_INVALID;
     const int mode = h->fitness_mode;
+    if (mode == NICNES_FITNESS_XENT)
+        return fail(h, NICNES_ERR_UNSUPPORTED, "nic_es: the xent fitness is not implemented (greedy, greedy_*)");
     if (mode >= NICNES_FITNESS_SAMPLE)
         return fail(h, NICNES_ERR_UNSUPPORTED, "nic_es: the sampled fitness modes are not implemented (greedy, greedy_*)");
     if ((h->dec_S != 0 && h->dec_S != 1) || (h->dec_G != 0 && h->dec_G != 4))

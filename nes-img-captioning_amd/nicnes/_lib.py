@@ -33,7 +33,8 @@ EXPORTS = ['nicnes_param_count', 'nicnes_param_offsets', 'nicnes_param_offsets_l
            'nicnes_es_offspring', 'nicnes_es_select', 'nicnes_es_advance', 'nicnes_es_set_elite',
            'nicnes_es_load_theta', 'nicnes_set_decode_es', 'nicnes_decode_path_es', 'nicnes_allgather_fitness_es',
            'nicnes_sensitivity_es', 'nicnes_set_sensitivity_es', 'nicnes_get_sensitivity_es', 'nicnes_set_mutation_divide_es',
-           'nicnes_trainset_create', 'nicnes_trainset_write_fc', 'nicnes_trainset_destroy', 'nicnes_draw_batches', 'nicnes_test_batch_state']
+           'nicnes_trainset_create', 'nicnes_trainset_write_fc', 'nicnes_trainset_destroy', 'nicnes_draw_batches', 'nicnes_test_batch_state',
+           'nicnes_xent_rows', 'nicnes_xent_batch_rows', 'nicnes_test_xent_steps', 'nicnes_split_xent']
 
 
 class NicnesConfig(ctypes.Structure):
@@ -131,6 +132,10 @@ def lib(path=None):
         'nicnes_split_evaluate_beam': (c.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         'nicnes_test_beam_select': (c.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         'nicnes_set_beam_waves': (c.c_int, [vp, i32]),
+        'nicnes_xent_rows': (c.c_int, [vp, i32, i32, vp, vp, vp]),
+        'nicnes_xent_batch_rows': (c.c_int, [vp, i32, vp]),
+        'nicnes_test_xent_steps': (c.c_int, [vp, u64, i32, i32, f32, vp, i32, vp, vp, vp]),
+        'nicnes_split_xent': (c.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
         'nicnes_trainset_create': (c.c_int, [vp, vp, i32, vp, i32, vp, c.POINTER(vp), vp]),
         'nicnes_trainset_write_fc': (c.c_int, [vp, vp, i32, i32, vp, vp]),
         'nicnes_trainset_destroy': (c.c_int, [vp, vp]),

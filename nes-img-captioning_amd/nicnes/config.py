@@ -41,6 +41,12 @@ ModelOptions = namedtuple('ModelOptions', field_names=_model_opt_fields, default
 GREEDY_FITNESS = ('greedy', 'greedy_logprob', 'greedy_expprob', 'greedy_linprob', 'greedy_avgprob')
 SAMPLED_FITNESS = ('sample', 'self_critical', 'sc_loss')
 FITNESS = GREEDY_FITNESS + SAMPLED_FITNESS          # every Fitness enum value (src/captioning/policies.py:22-35)
+# An extension of the reference's Fitness enum (it has no such member; its xent models, mscoco_es.json's
+# pretrained/bu_xent_09.pth, come from upstream cross-entropy training): the teacher-forced likelihood of the batch's
+# label rows, -loss of self-critical.pytorch's LanguageModelCriterion (include/nicnes.h NICNES_FITNESS_XENT). nic_nes
+# with plain mutations at rnn_size = input_encoding_size = 128 without layer_n only.
+XENT_FITNESS = ('xent',)
+ENGINE_FITNESS = FITNESS + XENT_FITNESS
 
 
 class NotSupported(ValueError):
@@ -91,9 +97,9 @@ class ExperimentSpec:
         po, mo = self.policy_options, self.model_options
         if po.net != 'fc_caption':
             raise NotSupported('net %r: the engine implements fc_caption' % po.net)
-        if self.fitness not in FITNESS:
-            raise NotSupported("fitness %r: the engine implements %s (src/captioning/policies.py:22-61)"
-                               % (po.fitness, ', '.join(FITNESS)))
+        if self.fitness not in ENGINE_FITNESS:
+            raise NotSupported("fitness %r: the engine implements %s (src/captioning/policies.py:22-61) and its own %s"
+                               % (po.fitness, ', '.join(FITNESS), ', '.join(XENT_FITNESS)))
         if po.vbn or mo.vbn or mo.vbn_e:
             raise NotSupported('virtual batch norm is not implemented by the engine (it normalises over the batch; '
                                'layer_n, a function of one row, is)')
@@ -103,6 +109,13 @@ class ExperimentSpec:
                                "(self.nb_params on Sensitivity, safe_mutations.py:125)")
         if m not in ('', 'SM-G-SUM', 'SM-VECTOR', 'SM-PROPORTIONAL'):
             raise NotSupported('safe_mutations %r (Mutation, src/algorithm/nets.py:16-21)' % m)
+        if self.fitness in XENT_FITNESS:
+            # what nicnes_set_fitness_mode and the xent evaluate refuse is refused here, never ignored
+            if mo.layer_n or is_wide(mo):
+                raise NotSupported('fitness %r: the teacher-forced forward runs rnn_size = input_encoding_size = 128 '
+                                   'models without layer_n only' % self.fitness)
+            if m:
+                raise NotSupported('fitness %r with safe_mutations %r: plain mutations only' % (self.fitness, m))
         if mo.layer_n:
             # a layer_n handle is refused what a wide one is (nicnes_set_fitness_mode, nicnes_sum_sensitivity)
             if self.fitness in SAMPLED_FITNESS:

@@ -290,14 +290,23 @@ class Engine:
 
     # Fitness enum values the engine implements (src/captioning/policies.py:22-35) -> nicnes.h codes
     FITNESS_MODES = {'greedy': 0, 'greedy_logprob': 1, 'greedy_expprob': 2, 'greedy_linprob': 3,
-                     'greedy_avgprob': 4, 'sample': 5, 'self_critical': 6, 'sc_loss': 7}
+                     'greedy_avgprob': 4, 'sample': 5, 'self_critical': 6, 'sc_loss': 7,
+                     'xent': 8}      # 'xent': the engine's extension (teacher-forced likelihood of the label rows)
     SAMPLED_MODES = (5, 6, 7)
+    XENT_MODE = 8
 
     def set_fitness_mode(self, fitness):
-        """Fitness criterion by its experiment-JSON name (policy_options.fitness) or nicnes.h code."""
-        code = self.FITNESS_MODES.get(fitness, fitness) if isinstance(fitness, str) else int(fitness)
-        if isinstance(code, str):
-            code = -1
+        """Fitness criterion by its experiment-JSON name (policy_options.fitness), or by the nicnes.h code of a member
+        of the reference's Fitness enum (0..7). The engine's own extension has no place in that enum and is chosen by
+        its name, 'xent', only: an integer beyond the enum stays an error here, as it was before the extension took
+        the next code of the C ABI (NICNES_FITNESS_XENT = 8)."""
+        if isinstance(fitness, str):
+            code = self.FITNESS_MODES.get(fitness, -1)
+        else:
+            code = int(fitness)
+            if code == self.XENT_MODE:
+                raise ValueError("set_fitness_mode(%r): integer codes name the reference's Fitness enum (0..7); "
+                                 "choose the engine's extension by its name, 'xent'" % (fitness,))
         check(self.L.nicnes_set_fitness_mode(self.h, code), self.h, 'set_fitness_mode(%r)' % (fitness,))
         self.fitness_mode = code
 
@@ -324,6 +333,47 @@ class Engine:
                                                  self._stream()), self.h, 'evaluate')
         out = (fit,) + ((seq,) if return_seq else ()) + ((lp,) if return_lp else ())
         return out if len(out) > 1 else fit
+
+    def xent_batch_rows(self, batch=0):
+        """Label rows (reference rows) of batch `batch` of the batches held: the rows an 'xent' evaluate runs."""
+        out = ctypes.c_int32(0)
+        check(self.L.nicnes_xent_batch_rows(self.h, int(batch), ctypes.byref(out)), self.h, 'xent_batch_rows')
+        return int(out.value)
+
+    def xent_rows(self, cand=0, batch=0):
+        """After an evaluate in 'xent' mode: candidate cand's (member k sign s: 2 k + s; evaluate_theta: 0) per-row
+        (lp_sum [rows] fp64, n_tok [rows] int32) over the label rows of its batch `batch`; tensors on the GPU."""
+        rows = self.xent_batch_rows(batch)
+        lp = torch.empty(rows, dtype=torch.float64, device=self.device)
+        nt = torch.empty(rows, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_xent_rows(self.h, int(cand), rows, _ptr(lp), _ptr(nt), self._stream()), self.h, 'xent_rows')
+        return lp, nt
+
+    def test_xent_steps(self, iteration=0, member_begin=0, count=1, sigma=0.0, member_batch=None, theta_batch=None):
+        """Test entry: the 'xent' evaluate returning every counted target's log-prob, 0 elsewhere. Members: (fitness
+        [count, 2], lp [count, 2, stride, T + 1]) with stride = the largest batch's label rows; theta_batch = b: theta
+        itself on batch b, (fitness [1], lp [rows of b, T + 1]). Tensors on the GPU (synchronises)."""
+        T1 = self.cfg.seq_length + 1
+        mb = None
+        if theta_batch is not None:
+            fit = torch.empty(1, dtype=torch.float64, device=self.device)
+            lp = torch.empty((self.xent_batch_rows(theta_batch), T1), dtype=torch.float32, device=self.device)
+        else:
+            stride = max(self.xent_batch_rows(b) for b in range(getattr(self, 'n_batches', 1)))
+            fit = torch.empty((count, 2), dtype=torch.float64, device=self.device)
+            lp = torch.empty((count, 2, stride, T1), dtype=torch.float32, device=self.device)
+            if member_batch is not None:
+                mb_np = np.ascontiguousarray(np.asarray(member_batch, np.int32))
+                if mb_np.shape != (count,):
+                    raise ValueError('member_batch needs one entry per member')
+                mb = mb_np.ctypes.data_as(ctypes.c_void_p)
+        with torch.cuda.device(self.device):
+            check(self.L.nicnes_test_xent_steps(self.h, ctypes.c_uint64(iteration), int(member_begin), int(count),
+                                                ctypes.c_float(sigma), mb, -1 if theta_batch is None else int(theta_batch),
+                                                _ptr(fit), _ptr(lp), self._stream()), self.h, 'test_xent_steps')
+            torch.cuda.current_stream().synchronize()
+        return fit, lp
 
     def set_rows_per_image(self, n=1):
         """Sampled modes: decode n rows per image of the batch (the reference's seq_per_img copies, each with
@@ -884,6 +934,7 @@ class Split:
             rows = [np.asarray(g, np.int32).reshape(-1, T) for g in gts]
             start = np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(np.int32)
             refs_np = np.ascontiguousarray(np.concatenate(rows, 0))
+            self._row_start = start
             # as set_batches: an id outside the vocabulary would alias another word in the 14-bit key fields
             if refs_np.size and (refs_np.min() < 0 or refs_np.max() > e.cfg.vocab_size):
                 raise ValueError('reference token outside [0, vocab_size = %d]: min %d, max %d'
@@ -959,6 +1010,25 @@ class Split:
             check(e.L.nicnes_split_decode_beam(e.h, self.sp, first, count, beam, _ptr(seq), _ptr(score), e._stream()),
                   e.h, 'split_decode_beam')
         return (seq, score) if return_score else seq
+
+    def xent(self, first=0, count=None):
+        """The teacher-forced cross-entropy of the engine's current theta on the label rows of images [first, first +
+        count) (nicnes_split_xent; the definition is NICNES_FITNESS_XENT's): {'loss': the per-token mean of -log p,
+        'perplexity': exp(loss), 'tokens': the targets counted (each row's words plus one end token), 'lp_sum' [rows]
+        fp64 and 'n_tok' [rows] int32 per label row, tensors on the GPU}. One enqueue, then one read-back of the three
+        scalars; the fitness mode, df table, batches and mutation stay as they are."""
+        e = self.engine
+        first, count = self._range(first, count)
+        rows = int(self._row_start[first + count] - self._row_start[first]) if self.has_refs else 0
+        out2 = torch.empty(2, dtype=torch.float64, device=e.device)
+        tok = torch.empty(1, dtype=torch.int64, device=e.device)
+        lp = torch.empty(rows, dtype=torch.float64, device=e.device)
+        nt = torch.empty(rows, dtype=torch.int32, device=e.device)
+        with torch.cuda.device(e.device):
+            check(e.L.nicnes_split_xent(e.h, self.sp, first, count, _ptr(out2), _ptr(tok), _ptr(lp), _ptr(nt),
+                                        e._stream()), e.h, 'split_xent')
+        o = out2.cpu().numpy()
+        return {'loss': float(o[0]), 'perplexity': float(o[1]), 'tokens': int(tok.item()), 'lp_sum': lp, 'n_tok': nt}
 
     def _outputs(self, count, rows):
         e = self.engine

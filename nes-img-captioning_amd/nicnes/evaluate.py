@@ -7,7 +7,9 @@ eval_on_test.py (CaptPolicy.accuracy_on -> eval_split, captioning/eval_utils.py:
 Writes {'stats': {'Bleu_1'..'Bleu_4', 'ROUGE_L', 'CIDEr'}, 'predictions': [{'image_id', 'caption'}]} as JSON. The
 metrics are computed on the split's label rows (word ids, captions cut to seq_length words, rare words as UNK), not
 on PTB-tokenised raw annotations; METEOR and SPICE (java) are not computed (nicnes.validation). --beam_size K (1..8)
-decodes with the engine's beam search (sum of log-probs, no length normalisation) instead of greedily.
+decodes with the engine's beam search (sum of log-probs, no length normalisation) instead of greedily. --xent adds
+the teacher-forced validation loss and perplexity of theta on the split's label rows to the stats ('val_loss',
+'val_perplexity') and prints them.
 """
 import argparse
 import importlib
@@ -25,6 +27,8 @@ def parse_args(argv=None):
     ap.add_argument('--incl_gts', action='store_true', help='add the reference captions to every prediction')
     ap.add_argument('--beam_size', type=int, default=None, choices=range(1, 9), metavar='K',
                     help='beam width 1..8 of the decode (default: greedy)')
+    ap.add_argument('--xent', action='store_true',
+                    help='add the teacher-forced cross-entropy (val_loss, val_perplexity) of the label rows')
     ap.add_argument('--data_root', default='.', help="directory the caption_options paths are relative to")
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--engine_factory', default=None, help='module:function(spec, args) -> engine (default: an Engine)')
@@ -52,8 +56,11 @@ def main(argv=None):
         engine = default_engine(spec, args)
     EnginePolicy(engine).set_model(args.model)
     num = args.num if args.num is not None else spec.config.num_val_items
-    validator = Validator(engine, loader, args.split, 5000 if num is None else int(num), beam_size=args.beam_size)
+    extra = {'xent': True} if args.xent else {}
+    validator = Validator(engine, loader, args.split, 5000 if num is None else int(num), beam_size=args.beam_size, **extra)
     stats, predictions = validator.eval_split(incl_gts=args.incl_gts)
+    if args.xent:
+        print('loss %.6f perplexity %.4f' % (stats['val_loss'], stats['val_perplexity']))
     with open(args.out, 'w') as f:
         json.dump({'stats': stats, 'predictions': predictions}, f)
     validator.close()

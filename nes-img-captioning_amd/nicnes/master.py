@@ -117,6 +117,7 @@ class EngineMaster:
         self.validator = validator
         self.validate = validator is not None
         self.val_score = None
+        self.val_loss = None                    # a Validator(xent=True)'s validation loss (rank 0; recorded, never ranked)
         self.best_val_score = float('-inf')
         self.best_elites = []                   # [(path, score)]: Podium with num_elites = 1
         self._batch_key = None
@@ -173,6 +174,8 @@ class EngineMaster:
         if not self.validate:
             return None
         score = self.policy.accuracy_on(self.validator) if self.rank == 0 else 0.0
+        if self.rank == 0:
+            self.val_loss = (getattr(self.policy, 'last_lang_stats', None) or {}).get('val_loss')
         if self.world > 1:
             t = torch.zeros((1, 2), dtype=torch.float64, device=self.e.device)
             t[0, 0] = score
@@ -202,6 +205,8 @@ class EngineMaster:
                'batch_size': self.sched.batch_size, 'step_time': time.time() - t0}
         if self.validate:
             rec['val_score'], rec['best_val_score'] = self.val_score, self.best_val_score
+            if self.val_loss is not None:       # beside the score; the best-theta rule stays on CIDEr
+                rec['val_loss'] = self.val_loss
         self.stats.append(rec)
         return rec
 

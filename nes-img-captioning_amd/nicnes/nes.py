@@ -234,6 +234,7 @@ class EnginePolicy:
         """CaptPolicy.accuracy_on (policies.py:130-143): the CIDEr of eval_split of the current theta on the
         validator's split (nicnes.validation.Validator: the greedy decode and COCOEvalCap's metrics on the GPU)."""
         lang_stats, _ = validator.eval_split()
+        self.last_lang_stats = lang_stats       # (EngineMaster reads a Validator(xent=True)'s val_loss from here)
         return float(lang_stats['CIDEr'])
 
 

@@ -73,9 +73,14 @@ class Validator:
     labels.labels[label_start_ix[ix] - 1 : label_end_ix[ix]], the gts of get_batch).
 
     beam_size (1..8; None: greedy, the reference's eval during training) decodes with the engine's beam search
-    (Split.decode_beam: the sum of log-probs, no length normalisation), as test-time evaluation usually does."""
+    (Split.decode_beam: the sum of log-probs, no length normalisation), as test-time evaluation usually does.
 
-    def __init__(self, engine, loader, split='val', num=5000, beam_size=None):
+    xent=True adds the validation loss to eval_split's stats: 'val_loss' (the teacher-forced cross-entropy of theta on
+    the split's label rows, Split.xent: what self-critical.pytorch's eval_split reports beside the language metrics)
+    and 'val_perplexity'."""
+
+    def __init__(self, engine, loader, split='val', num=5000, beam_size=None, xent=False):
+        self.xent = bool(xent)
         if beam_size is not None and not 1 <= int(beam_size) <= 8:
             raise ValueError('beam_size must be in 1..8, got %r' % (beam_size,))
         self.beam_size = None if beam_size is None else int(beam_size)
@@ -98,6 +103,9 @@ class Validator:
         """(lang_stats, predictions): COCOEvalCap's dict and [{'image_id', 'caption'}] in split order; incl_gts adds
         the reference strings as 'gts'."""
         stats, seq = self.split.evaluate(return_seq=True, **self._beam())
+        if self.xent:
+            x = self.split.xent()
+            stats['val_loss'], stats['val_perplexity'] = x['loss'], x['perplexity']
         seq = seq.cpu().numpy() if hasattr(seq, 'cpu') else np.asarray(seq)
         sents = decode_sequence(self.loader.ix_to_word, seq)
         preds = []
