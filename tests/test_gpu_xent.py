@@ -14,7 +14,8 @@ Cases (F = 128, three members, sigma 0.01; images of 1..7 label rows throughout)
   d  V1 9488  T 3   33 rows   the workload's vocabulary
   e  V1 68    T 1   1 row     one image, one row, one word
 Targets are planted at ids 0, 3, 4, 31, 32, 63, 64 and V1 - 1 (those below V1), so every lane half ((id >> 2) & 1), both
-32-id tiles of a stage, the first and the last stage and the partial one own a target."""
+32-id tiles of a stage, the first and the last stage and the partial one own a target.
+Other F, more rows, slabs, pseudo-members, windows, draws and zeros inside labels: tests/test_gpu_xent_shapes.py."""
 import numpy as np
 import pytest
 
